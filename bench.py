@@ -11,15 +11,22 @@ The timed region is ONE call of the library's plain entry point - bpr1cs_prove_b
 created with NO options: window width, proofs per device job and jobs in flight are the library's defaults, so what is
 measured is what any caller of the C ABI gets (config keys `proofs_per_device_job`, `device_jobs` report what it chose).
 
-    python bench.py [--config c1|c2|c3|c4|c5|vsmt4_d128|vsmt2_d253] [--gpus N] [--steps K] [--warmup W] [--configs LIST]
+    python bench.py [--config c1|c2|c3|c4|c5|vsmt4_d128|vsmt2_d253] [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                    [--full [--configs LIST] [--latency 0|1] [--cpu-proofs P]]
 `--gpus N` with N > 1 launches N ranks by itself (python -m torch.distributed.run --nnodes=1 --nproc-per-node N, rendezvous on
 127.0.0.1) unless it already runs under a launcher (WORLD_SIZE set, which must then equal N); one rank per GPU over RCCL.
-After the headline the same run times the other BASELINE configurations (`configs` block of the JSON: c2, c3, c5 and the
-depths the reference ships, each with its proofs/s and a parity flag against the committed oracle digests).
 
-Prints ONE JSON line on rank 0 (contract in the task prompt), with `roofline` for the dominant kernel (batched fixed-base
-MSM, HIP-event timed on its own stream inside the library), `roofline_valu` (the integer ceiling that really binds it) and
-`cpu_baseline` (the oracle's C restatement timed on the host cores, rank 0, N=1 only).
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the outputs of the last timed step
+(`--dump-outputs DIR`: DIR/proofs.npy and DIR/commitments.npy, the bytes the caller receives as float32, shape (batch, bytes)
+and (batch, m, 32), and DIR/proof_index.npy; a seeded sample of the batch where it would pass 60 MB; under several ranks every
+rank writes its own, suffixed _rank<r>) and print ONE JSON line on rank 0 with
+`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the configuration and the setup seconds.
+
+`--full` adds, after the timed region: the device verifiers on one job's proofs (`verify`, `verify_batched`), `roofline` for the
+dominant kernel (batched fixed-base MSM, HIP-event timed on its own stream inside the library), `roofline_valu` (the integer
+ceiling that really binds it, with probes of its own), `cpu_baseline` (the oracle's C restatement timed on the host cores,
+rank 0, N=1 only), the `latency` block and the other BASELINE configurations (`configs` block: c2, c3, c5 and the depths the
+reference ships, each with its proofs/s and a parity flag against the committed oracle digests).
 """
 import argparse
 import hashlib
@@ -38,6 +45,7 @@ L, synth_scalar, sc, synth_rng_seed = wl.L, wl.synth_scalar, wl.sc, wl.synth_rng
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
 NOMINAL_MAD_LANE_OPS = 256 * 4 * 16 * 2.4e9   # v_mad_i64_i32 at a quarter of the lane rate (MI355X_MICROARCH.md: 256 CUs x 4 SIMDs, 2.4 GHz peak engine clock)
 MADS_PER_TABLE_ADD = 7 * 99   # 7 field multiplications (ge_madd_t) x (81 limb products + 9 fold + 9 carry re-entries) v_mad_i64_i32 / v_mad_u64_u32
+MAX_CPU_WORKERS = 15   # worker processes of the CPU baseline, forked from this process (which holds the GPU): 16 processes at most
 
 
 def build_workload(bp, levels, batch, n_leaves, seed_base):
@@ -199,11 +207,12 @@ def cpu_baseline(w, n_proofs, max_threads):
         phase = [a + b for a, b in zip(phase, ph)]
     dt1 = time.time() - t0
     model, logical, usable, quota = cpu_info()
-    threads = max(1, min(usable, max_threads, w["B"], math.ceil(quota) if quota else usable))
+    threads = max(1, min(usable, max_threads, w["B"], math.ceil(quota) if quota else usable, MAX_CPU_WORKERS))
     per_worker = max(1, min(w["B"] // threads, int(math.ceil(4.0 / max(dt1 / n_proofs, 1e-3)))))   # ~4 s of work per worker
     # one WORKER PROCESS per CPU (forked after the generators are warm; the children only run the C oracle and leave through
     # os._exit).  Threads of one process would serialise on the kernel's mmap lock: the oracle allocates and frees hundreds
-    # of MB per proof (256 threads: 30x slower per proof than one thread alone).
+    # of MB per proof (256 threads: 30x slower per proof than one thread alone).  The parent holds the GPU: each worker first
+    # closes every descriptor it inherited but its pipe, and there are at most MAX_CPU_WORKERS of them.
     sys.stdout.flush()
     t0 = time.time()
     kids = []
@@ -213,7 +222,8 @@ def cpu_baseline(w, n_proofs, max_threads):
         if pid == 0:
             code = 1
             try:
-                os.close(r)
+                os.closerange(3, wr)
+                os.closerange(wr + 1, os.sysconf("SC_OPEN_MAX"))
                 h = hashlib.sha256()
                 for i in range(per_worker):
                     h.update(one(k * per_worker + i)["proof"])
@@ -363,6 +373,28 @@ def measure(bp, lib, gens, circ, w, B, steps, warm_steps, barrier=None):
         barrier()
     dt = time.perf_counter() - t0
     return dt, proofs, comms, bp.last_prove_stats(lib)
+
+
+DUMP_BYTES_MAX = 60 * 10**6   # --dump-outputs writes at most this much (float32 = 4 bytes per output byte)
+
+
+def dump_outputs(path, proofs_raw, comms_raw, B, steps, plen, m, suffix=""):
+    """--dump-outputs: what the timed call handed its caller for its LAST step (proofs (steps - 1) * B .. steps * B - 1) as
+    float32 arrays, one value per byte: proofs<suffix>.npy (rows, plen), commitments<suffix>.npy (rows, m, 32) and
+    proof_index<suffix>.npy (rows,), the index of each row in the timed call.  All rows when they fit in DUMP_BYTES_MAX,
+    otherwise a fixed seeded sample of them, in order."""
+    import numpy as np
+    rows = np.arange(B)
+    fit = max(1, DUMP_BYTES_MAX // (4 * (plen + 32 * m)))
+    if fit < B:
+        rows = np.sort(np.random.default_rng(0).choice(B, fit, replace=False))
+    first = (steps - 1) * B
+    P = np.frombuffer(proofs_raw, dtype=np.uint8, count=steps * B * plen).reshape(steps * B, plen)[first:][rows]
+    C = np.frombuffer(comms_raw, dtype=np.uint8, count=steps * B * m * 32).reshape(steps * B, m, 32)[first:][rows]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "proofs%s.npy" % suffix), P.astype(np.float32))
+    np.save(os.path.join(path, "commitments%s.npy" % suffix), C.astype(np.float32))
+    np.save(os.path.join(path, "proof_index%s.npy" % suffix), (first + rows).astype(np.float64))
 
 
 LATENCY_SHAPE = ("the reference's own call shape - ONE proof per prove() inside its timed bracket (src/gadget_vsmt_4.rs:421-435, "
@@ -522,11 +554,15 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="proofs per GPU per step (0 = the configuration's)")
     ap.add_argument("--depth", type=int, default=32, help="c4 only: 4-ary tree levels (BASELINE: 32)")
     ap.add_argument("--leaves", type=int, default=0, help="c4 only: distinct synthetic leaves cycled over the batch (0 = one per proof)")
-    ap.add_argument("--cpu-proofs", type=int, default=-1, help="proofs timed on ONE thread of the CPU oracle (0 = skip the CPU leg, -1 = the configuration's)")
-    ap.add_argument("--cpu-threads", type=int, default=128, help="upper bound of the all-cores CPU run")
-    ap.add_argument("--configs", default="default", help="other configurations timed after the headline (rank 0 of a 1-GPU run): 'default' = c4,c3,c1,c2,c5,vsmt4_d128,vsmt2_d253 (those on the headline's generator tables first) "
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed region, write what its last step computed - the proof and commitment "
+                    "bytes of its `batch` proofs - as DIR/proofs.npy, DIR/commitments.npy and DIR/proof_index.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true", help="after the headline, everything else: verifiers, roofline figures and their probes, the CPU baseline, "
+                    "the `latency` block and the other configurations (off: the plain run measures the headline only)")
+    ap.add_argument("--cpu-proofs", type=int, default=-1, help="--full: proofs timed on ONE thread of the CPU oracle (0 = skip the CPU leg, -1 = the configuration's)")
+    ap.add_argument("--cpu-threads", type=int, default=128, help="--full: upper bound of the all-cores CPU run")
+    ap.add_argument("--configs", default="default", help="--full: other configurations timed after the headline (rank 0 of a 1-GPU run): 'default' = c4,c3,c1,c2,c5,vsmt4_d128,vsmt2_d253 (those on the headline's generator tables first) "
                     "for the default c4 run, 'none', or a comma list")
-    ap.add_argument("--latency", type=int, default=1, help="1 (default): the `latency` block - ONE proof per prove() call and 8 / 64 witnesses per call, c1 and c4 (1-GPU c4 runs)")
+    ap.add_argument("--latency", type=int, default=1, help="--full: 1 (default) adds the `latency` block - ONE proof per prove() call and 8 / 64 witnesses per call, c1 and c4 (1-GPU c4 runs)")
     ap.add_argument("--dry-run", action="store_true", help="CPU rehearsal of the launch / rendezvous / timing path (no prover)")
     # measuring options: anything given here is an EXPLICIT option of the generator handle (the default run sets none)
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="option of the generator handle (bpr1cs_gens_create_opts), e.g. unfold=3, job_proofs=1024, "
@@ -568,18 +604,20 @@ def main():
 
     # the library's own RCCL communicator for the sharded verifier (bpr1cs_verify_batch_sharded), created at start-up: RCCL brings
     # up its view of the runtime best in a young process, and every rank meets here before any of them holds 280 GB
+    # (--full only: a plain run has no verification leg)
     comm = None
-    try:
-        sh0 = importlib.import_module("bulletproofs-r1cs-gadgets_amd.sharding")
-        comm = sh0.make_comm(bp, rank, world, device="cuda" if dist is not None else None)
-    except Exception as e:  # pragma: no cover
-        print("bench.py: no RCCL communicator for the verification leg (%r): the torch collectives are used instead" % (e,), file=sys.stderr)
-    if dist is not None:   # all ranks use the same form
-        flag = torch.tensor([1 if comm is not None else 0], device="cuda", dtype=torch.int32)
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        if int(flag.item()) == 0 and comm is not None:
-            comm.close()
-            comm = None
+    if args.full:
+        try:
+            sh0 = importlib.import_module("bulletproofs-r1cs-gadgets_amd.sharding")
+            comm = sh0.make_comm(bp, rank, world, device="cuda" if dist is not None else None)
+        except Exception as e:  # pragma: no cover
+            print("bench.py: no RCCL communicator for the verification leg (%r): the torch collectives are used instead" % (e,), file=sys.stderr)
+        if dist is not None:   # all ranks use the same form
+            flag = torch.tensor([1 if comm is not None else 0], device="cuda", dtype=torch.int32)
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            if int(flag.item()) == 0 and comm is not None:
+                comm.close()
+                comm = None
     rccl_ranks = comm.world if comm is not None else None   # size of the library's own communicator (bpr1cs_comm_*)
 
     B = args.batch if args.batch > 0 else cfg["batch"]
@@ -618,61 +656,50 @@ def main():
         dt = float(t.item())
     msm_ms, msm_launches, msm_terms, phases = st["msm_ms"], st["msm_launches"], st["msm_terms"], st["phase_ms"]
     plen = circ.proof_len
-    Bj = min(st["job_proofs"], Bw)                  # one device job's worth of distinct proofs for the verification legs below
-    proofs = [proofs_raw[i * plen:(i + 1) * plen] for i in range(Bj)]
-    comms = [[comms_raw[(i * m + j) * 32:(i * m + j + 1) * 32] for j in range(m)] for i in range(Bj)]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, proofs_raw, comms_raw, B, steps, plen, m, "_rank%d" % rank if world > 1 else "")
 
-    gens.release_scratch()   # the verifiers below allocate their own scratch (8 GiB per vector at N = 262144): hand the prover's arenas back first
-    # Outside the timed region, on every rank: cross-proof batched verification of one job's proofs
-    # (bpr1cs_verify_batch_combined) and the path's only exchange step, an all_gather of one 32-byte point per rank.
     batched = None
-    try:
-        sh = importlib.import_module("bulletproofs-r1cs-gadgets_amd.sharding")
-        # one-shot calls are noisy (first-use allocations): both forms run twice, the faster run is reported
-        tb = ts = float("inf")
-        accepted = accepted_split = True
-        for _ in range(2):
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            try:   # fresh randomness for the weights (include/bpr1cs.h: batch_seed must not be predictable)
-                pt, wf = bp.verify_batch_combined(gens, circ, label, proofs, comms, Bj, os.urandom(32), index_base=rank * Bj)
-            except Exception:  # keep the collective below matched on every rank
-                pt, wf = b"\xff" * 32, False
-            pts, all_wf = sh.gather_partial_points(pt, wf, device="cuda" if dist is not None else None)
-            accepted = accepted and bool(all_wf) and bp.points_sum_is_identity(pts)
-            tb = min(tb, time.perf_counter() - t1)
-            # the multi-GPU form: shared-base MSM split by base range over the ranks (all_gather of the combined scalar vectors)
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            accepted_split = sh.verify_sharded(bp, gens, circ, label, proofs, comms, Bj, rank, world, rank * Bj, device="cuda" if dist is not None else None, comm=comm) and accepted_split
-            ts = min(ts, time.perf_counter() - t1)
-        batched = {"accepted_all": accepted, "proofs": Bj * world, "proofs_per_s": Bj * world / tb,
-                   "split_shared_base": {"accepted_all": accepted_split, "proofs_per_s": Bj * world / ts,
-                                         "note": "bpr1cs_verify_batch_sharded: ONE C-ABI call per rank (scalars, ncclAllGather of the scalar vectors, 1/world of the bases, ncclAllGather of 65 bytes)"},
-                   "note": "bpr1cs_verify_batch_combined + all_gather of one point per rank; not part of `value`"}
-    except Exception as e:  # pragma: no cover
-        batched = {"error": repr(e)}
+    if args.full:
+        Bj = min(st["job_proofs"], Bw)                  # one device job's worth of distinct proofs for the verification legs below
+        proofs = [proofs_raw[i * plen:(i + 1) * plen] for i in range(Bj)]
+        comms = [[comms_raw[(i * m + j) * 32:(i * m + j + 1) * 32] for j in range(m)] for i in range(Bj)]
+
+        gens.release_scratch()   # the verifiers below allocate their own scratch (8 GiB per vector at N = 262144): hand the prover's arenas back first
+        # Outside the timed region, on every rank: cross-proof batched verification of one job's proofs
+        # (bpr1cs_verify_batch_combined) and the path's only exchange step, an all_gather of one 32-byte point per rank.
+        try:
+            sh = importlib.import_module("bulletproofs-r1cs-gadgets_amd.sharding")
+            # one-shot calls are noisy (first-use allocations): both forms run twice, the faster run is reported
+            tb = ts = float("inf")
+            accepted = accepted_split = True
+            for _ in range(2):
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                try:   # fresh randomness for the weights (include/bpr1cs.h: batch_seed must not be predictable)
+                    pt, wf = bp.verify_batch_combined(gens, circ, label, proofs, comms, Bj, os.urandom(32), index_base=rank * Bj)
+                except Exception:  # keep the collective below matched on every rank
+                    pt, wf = b"\xff" * 32, False
+                pts, all_wf = sh.gather_partial_points(pt, wf, device="cuda" if dist is not None else None)
+                accepted = accepted and bool(all_wf) and bp.points_sum_is_identity(pts)
+                tb = min(tb, time.perf_counter() - t1)
+                # the multi-GPU form: shared-base MSM split by base range over the ranks (all_gather of the combined scalar vectors)
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                accepted_split = sh.verify_sharded(bp, gens, circ, label, proofs, comms, Bj, rank, world, rank * Bj, device="cuda" if dist is not None else None, comm=comm) and accepted_split
+                ts = min(ts, time.perf_counter() - t1)
+            batched = {"accepted_all": accepted, "proofs": Bj * world, "proofs_per_s": Bj * world / tb,
+                       "split_shared_base": {"accepted_all": accepted_split, "proofs_per_s": Bj * world / ts,
+                                             "note": "bpr1cs_verify_batch_sharded: ONE C-ABI call per rank (scalars, ncclAllGather of the scalar vectors, 1/world of the bases, ncclAllGather of 65 bytes)"},
+                       "note": "bpr1cs_verify_batch_combined + all_gather of one point per rank; not part of `value`"}
+        except Exception as e:  # pragma: no cover
+            batched = {"error": repr(e)}
 
     if rank == 0:
         value = world * B * steps / dt
         n = circ.n
-        lgN = N.bit_length() - 1
-        alg_bytes_per_proof = 576 * n + 448 * N + 64 * lgN - 96
-        # dominant kernel: algorithmic bytes = 64 B per scalar*point term + 32 B per output (MSM_BYTES(t) = 64 t + 32);
-        # every launch of the kernel is counted (commit sums, L/R of the un-folded rounds, the folded generators)
         jobs = max(1, st["jobs"])
-        launches_per_job = msm_launches / jobs
-        msm_alg_bytes = 64.0 * msm_terms + 32.0 * launches_per_job * B * steps
-        achieved = (msm_alg_bytes / 1e9) / (msm_ms / 1e3) if msm_ms > 0 else None
         tinfo = gens.table_info()
-        default_knobs = args.config == "c4" and args.depth == 32 and not options
-        khash = loaded_kernel_hash(bp)
-        traffic, traffic_ppl, traffic_src = pmc_profile("traffic", tinfo["format"], khash) if default_knobs else (None, None, None)
-        clock_ghz, clock_src = pmc_profile("clock", tinfo["format"], khash) if default_knobs else (None, None)
-        # integer ceilings, measured NOW on this device by the library's probes (bpr1cs_device_rates, ~80 ms each)
-        mad_rate, madd_chain_rate = bp.device_rates(0.08, lib)
-        adds = st["msm_adds"]
-        adds_per_s = adds / (msm_ms / 1e3) if msm_ms > 0 else None
         metric = cfg["metric"] or "R1CS proofs/sec (Poseidon VSMT-4 depth-%d)" % args.depth
         workload = cfg["workload"] or "gadget_vsmt_4 sparse-Merkle depth-%d membership (Poseidon 4:1 inverse S-box, 148 rounds)" % args.depth
         out = {
@@ -688,108 +715,127 @@ def main():
                        "ipa_unfold_rounds": options.get("unfold", 4), "options": options or None, "rccl_ranks": rccl_ranks,
                        "table_window_bits": tinfo["window_bits"], "table_windows": tinfo["windows"], "table_format": tinfo["format"],
                        "table_bytes": tinfo["bytes"]},
-            "roofline": {"bound": "hbm", "kernel": "k_msm_fixed2 (batched fixed-base MSM over the generator tables; a launch carries 1-4 sums)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
-                         "traffic": (traffic * st["job_proofs"] / traffic_ppl) if traffic else None,
-                         "traffic_source": traffic_src, "kernel_isa_sha256": khash,
-                         "traffic_note": "PMC FETCH_SIZE + WRITE_SIZE per launch from the named profile - quoted only when the profile is stamped with the ISA hash of the k_msm_fixed2 build this run has loaded, null otherwise (separate "
-                                         "rocprofv3 --pmc passes; scaled by proofs per launch if the profiled run used another job size); as reported by the "
-                                         "counters: on gfx950 FETCH_SIZE under-reports wide reads 2x and is uncalibrated for 128-byte gathers - a lower bound",
-                         "avg_launch_ms": (msm_ms / msm_launches) if msm_launches else None, "launches_per_step": msm_launches / steps,
-                         "launches_per_device_job": launches_per_job,
-                         "alg_bytes_per_launch": (msm_alg_bytes / msm_launches) if msm_launches else None,
-                         "note": "achieved/frac use ALGORITHMIC bytes (64 B per scalar*point term); the kernel is bound by integer multiply-add issue "
-                                 "and by the power its table gathers cost (DVFS), not by HBM bandwidth - see roofline_valu and DESIGN.md"},
-            # second, honest ceiling: 32-bit integer multiply-add issue.  One table addition = 693 multiply-adds;
-            # peak = measured v_mad_i64_i32 rate of this device / 693, and the NOMINAL quarter-rate ceiling beside it.
-            "roofline_valu": {"bound": "valu-int32-mad", "unit": "G table-add/s",
-                              "achieved": adds_per_s / 1e9 if adds_per_s else None,
-                              "peak": mad_rate / MADS_PER_TABLE_ADD / 1e9,
-                              "frac": (adds_per_s / (mad_rate / MADS_PER_TABLE_ADD)) if adds_per_s else None,
-                              "peak_nominal": NOMINAL_MAD_LANE_OPS / MADS_PER_TABLE_ADD / 1e9,
-                              "frac_nominal": (adds_per_s / (NOMINAL_MAD_LANE_OPS / MADS_PER_TABLE_ADD)) if adds_per_s else None,
-                              "mad_lane_ops_per_s": mad_rate, "mad_lane_ops_per_s_nominal": NOMINAL_MAD_LANE_OPS, "mads_per_table_add": MADS_PER_TABLE_ADD,
-                              "ge_madd_t_chain_G_per_s": madd_chain_rate / 1e9,
-                              "frac_of_madd_chain": (adds_per_s / madd_chain_rate) if adds_per_s else None,
-                              "effective_clock_ghz": clock_ghz, "effective_clock_source": clock_src,
-                              "note": "peak = sustained v_mad_i64_i32 lane-ops/s measured in this run (bpr1cs_device_rates) / 693 multiply-adds per "
-                                      "table addition; peak_nominal = 256 CUs x 4 SIMDs x 16 lanes per cycle (a 64-wide 64-bit multiply-add issues "
-                                      "over 4 cycles) x 2.4 GHz = 39.3 T lane-ops/s / 693; ge_madd_t chain = the same additions on register operands "
-                                      "(no gathers); effective clock of the kernel = GRBM_GUI_ACTIVE / 8 XCDs / duration from the named profile of this "
-                                      "build; zero scalars / zero digits are counted in `achieved`"},
-            "hbm_frac_whole_path": value / world * alg_bytes_per_proof / (HBM_PEAK_GBS * 1e9),
-            "phase_ms_per_device_job": {k: v / jobs for k, v in zip(["total", "inputs+commitV", "rng||witness", "commit_msm", "poly", "ipa"], phases)},
-            "setup_s": {"witness_trees": t_witness, "circuit_compile": t_compile, "generator_tables": t_gens},
         }
-        # outside the timed region: the device verifier (Verifier::verify, one mega-check MSM per proof) on one job's proofs
-        try:
-            tv = time.perf_counter()
-            oks = bp.verify_batch(gens, circ, label, proofs, comms, Bj)
-            tv = time.perf_counter() - tv
-            out["verify"] = {"accepted": sum(oks), "of": Bj, "proofs_per_s": Bj / tv, "note": "bpr1cs_verify_batch, not part of `value`"}
-        except Exception as e:  # pragma: no cover
-            out["verify"] = {"error": repr(e)}
-        out["verify_batched"] = batched
-        n_cpu = cfg["cpu_proofs"] if args.cpu_proofs < 0 else args.cpu_proofs
-        if world == 1 and n_cpu > 0:
-            cb, cproofs = cpu_baseline(w, n_cpu, args.cpu_threads)
-            out["cpu_baseline"] = cb
-            if cproofs is not None:
-                out["parity_vs_cpu_oracle"] = all(cproofs[j] == proofs[j] for j in range(len(cproofs)))
-        else:
-            out["cpu_baseline"] = None
-        # the reference's own call shape: one proof per prove() (and 8 / 64 witnesses per call), c4 on the headline's tables, c1 on its own
-        if world == 1 and args.latency and args.config == "c4" and args.depth == 32:
+        if args.full:
+            lgN = N.bit_length() - 1
+            alg_bytes_per_proof = 576 * n + 448 * N + 64 * lgN - 96
+            # dominant kernel: algorithmic bytes = 64 B per scalar*point term + 32 B per output (MSM_BYTES(t) = 64 t + 32);
+            # every launch of the kernel is counted (commit sums, L/R of the un-folded rounds, the folded generators)
+            launches_per_job = msm_launches / jobs
+            msm_alg_bytes = 64.0 * msm_terms + 32.0 * launches_per_job * B * steps
+            achieved = (msm_alg_bytes / 1e9) / (msm_ms / 1e3) if msm_ms > 0 else None
+            default_knobs = args.config == "c4" and args.depth == 32 and not options
+            khash = loaded_kernel_hash(bp)
+            traffic, traffic_ppl, traffic_src = pmc_profile("traffic", tinfo["format"], khash) if default_knobs else (None, None, None)
+            clock_ghz, clock_src = pmc_profile("clock", tinfo["format"], khash) if default_knobs else (None, None)
+            # integer ceilings, measured NOW on this device by the library's probes (bpr1cs_device_rates, ~80 ms each)
+            mad_rate, madd_chain_rate = bp.device_rates(0.08, lib)
+            adds = st["msm_adds"]
+            adds_per_s = adds / (msm_ms / 1e3) if msm_ms > 0 else None
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": "k_msm_fixed2 (batched fixed-base MSM over the generator tables; a launch carries 1-4 sums)",
+                             "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
+                             "traffic": (traffic * st["job_proofs"] / traffic_ppl) if traffic else None,
+                             "traffic_source": traffic_src, "kernel_isa_sha256": khash,
+                             "traffic_note": "PMC FETCH_SIZE + WRITE_SIZE per launch from the named profile - quoted only when the profile is stamped with the ISA hash of the k_msm_fixed2 build this run has loaded, null otherwise (separate "
+                                             "rocprofv3 --pmc passes; scaled by proofs per launch if the profiled run used another job size); as reported by the "
+                                             "counters: on gfx950 FETCH_SIZE under-reports wide reads 2x and is uncalibrated for 128-byte gathers - a lower bound",
+                             "avg_launch_ms": (msm_ms / msm_launches) if msm_launches else None, "launches_per_step": msm_launches / steps,
+                             "launches_per_device_job": launches_per_job,
+                             "alg_bytes_per_launch": (msm_alg_bytes / msm_launches) if msm_launches else None,
+                             "note": "achieved/frac use ALGORITHMIC bytes (64 B per scalar*point term); the kernel is bound by integer multiply-add issue "
+                                     "and by the power its table gathers cost (DVFS), not by HBM bandwidth - see roofline_valu and DESIGN.md"},
+                # second, honest ceiling: 32-bit integer multiply-add issue.  One table addition = 693 multiply-adds;
+                # peak = measured v_mad_i64_i32 rate of this device / 693, and the NOMINAL quarter-rate ceiling beside it.
+                "roofline_valu": {"bound": "valu-int32-mad", "unit": "G table-add/s",
+                                  "achieved": adds_per_s / 1e9 if adds_per_s else None,
+                                  "peak": mad_rate / MADS_PER_TABLE_ADD / 1e9,
+                                  "frac": (adds_per_s / (mad_rate / MADS_PER_TABLE_ADD)) if adds_per_s else None,
+                                  "peak_nominal": NOMINAL_MAD_LANE_OPS / MADS_PER_TABLE_ADD / 1e9,
+                                  "frac_nominal": (adds_per_s / (NOMINAL_MAD_LANE_OPS / MADS_PER_TABLE_ADD)) if adds_per_s else None,
+                                  "mad_lane_ops_per_s": mad_rate, "mad_lane_ops_per_s_nominal": NOMINAL_MAD_LANE_OPS, "mads_per_table_add": MADS_PER_TABLE_ADD,
+                                  "ge_madd_t_chain_G_per_s": madd_chain_rate / 1e9,
+                                  "frac_of_madd_chain": (adds_per_s / madd_chain_rate) if adds_per_s else None,
+                                  "effective_clock_ghz": clock_ghz, "effective_clock_source": clock_src,
+                                  "note": "peak = sustained v_mad_i64_i32 lane-ops/s measured in this run (bpr1cs_device_rates) / 693 multiply-adds per "
+                                          "table addition; peak_nominal = 256 CUs x 4 SIMDs x 16 lanes per cycle (a 64-wide 64-bit multiply-add issues "
+                                          "over 4 cycles) x 2.4 GHz = 39.3 T lane-ops/s / 693; ge_madd_t chain = the same additions on register operands "
+                                          "(no gathers); effective clock of the kernel = GRBM_GUI_ACTIVE / 8 XCDs / duration from the named profile of this "
+                                          "build; zero scalars / zero digits are counted in `achieved`"},
+                "hbm_frac_whole_path": value / world * alg_bytes_per_proof / (HBM_PEAK_GBS * 1e9),
+            })
+        out["phase_ms_per_device_job"] = {k: v / jobs for k, v in zip(["total", "inputs+commitV", "rng||witness", "commit_msm", "poly", "ipa"], phases)}
+        out["setup_s"] = {"witness_trees": t_witness, "circuit_compile": t_compile, "generator_tables": t_gens}
+        if args.full:
+            # outside the timed region: the device verifier (Verifier::verify, one mega-check MSM per proof) on one job's proofs
             try:
-                gens.release_scratch()
-                lat = {"call_shape": LATENCY_SHAPE}
-                lat["c4"] = run_latency(bp, lib, "c4", wl.vsmt4(bp, None, 32, 64, 64, 0), gens, "c4_vsmt4_d32_x2024")
-                gens.release_scratch()
-                g1 = bp.Gens(128)
-                lat["c1"] = run_latency(bp, lib, "c1", wl.bound_check64(64), g1, "c1_bound_check64_x4096")
-                g1.close()
-                if n_cpu > 0:   # the CPU port on the single-prover configuration (BASELINE config 1), one thread
-                    cb1, _ = cpu_baseline(wl.bound_check64(64), 32, 1)
-                    st1c = (cb1.get("single_thread") or {}).get("value")
-                    if st1c:
-                        lat["c1"]["cpu_port_ms_per_proof"] = 1e3 / st1c
-                        lat["c1"]["speedup_b1_vs_cpu_port_1_thread"] = (1e3 / st1c) / lat["c1"]["b1"]["ms_per_proof"]
-                cb = out.get("cpu_baseline") or {}
-                st1 = (cb.get("single_thread") or {}).get("value")
-                if st1:
-                    lat["c4"]["cpu_port_ms_per_proof"] = 1e3 / st1
-                    lat["c4"]["speedup_b1_vs_cpu_port_1_thread"] = (1e3 / st1) / lat["c4"]["b1"]["ms_per_proof"]
-                out["latency"] = lat
+                tv = time.perf_counter()
+                oks = bp.verify_batch(gens, circ, label, proofs, comms, Bj)
+                tv = time.perf_counter() - tv
+                out["verify"] = {"accepted": sum(oks), "of": Bj, "proofs_per_s": Bj / tv, "note": "bpr1cs_verify_batch, not part of `value`"}
             except Exception as e:  # pragma: no cover
-                out["latency"] = {"error": repr(e)}
-        # the other BASELINE configurations, each a short run of its own with the library's defaults (1-GPU runs only)
-        which = args.configs
-        if which == "default":
-            which = "c4,c3,c1,c2,c5,vsmt4_d128,vsmt2_d253" if (args.config == "c4" and args.depth == 32 and not options and world == 1) else "none"
-        if which != "none" and world == 1:
-            circ.close()
-            gens_by_cap = {N: gens}
-            blk = {}
-            for name in [x for x in which.split(",") if x]:
-                t1 = time.time()
+                out["verify"] = {"error": repr(e)}
+            out["verify_batched"] = batched
+            n_cpu = cfg["cpu_proofs"] if args.cpu_proofs < 0 else args.cpu_proofs
+            if world == 1 and n_cpu > 0:
+                cb, cproofs = cpu_baseline(w, n_cpu, args.cpu_threads)
+                out["cpu_baseline"] = cb
+                if cproofs is not None:
+                    out["parity_vs_cpu_oracle"] = all(cproofs[j] == proofs[j] for j in range(len(cproofs)))
+            else:
+                out["cpu_baseline"] = None
+            # the reference's own call shape: one proof per prove() (and 8 / 64 witnesses per call), c4 on the headline's tables, c1 on its own
+            if world == 1 and args.latency and args.config == "c4" and args.depth == 32:
                 try:
-                    if name == args.config and cfg.get("fixture") and "fixture_build" in cfg and N in gens_by_cap:
-                        # the headline itself: its throughput is `value`; here EVERY proof of the fixture batch against the oracle digests
-                        fw = cfg["fixture_build"](bp)
-                        fcirc = bp.CompiledGadget(fw["gadget"], fw["ip"], fw["sp"])
-                        fproofs, _ = bp.prove_batch_raw(gens, fcirc, fw["label"], fw["values"], fw["blindings"], fw["seeds"], fw["B"])
-                        blk[name] = {"metric": metric, "value": value, "unit": "proofs/s", "note": "the headline of this line", "parity": fixture_parity(cfg["fixture"], fw, fproofs, fcirc.proof_len)}
-                        fcirc.close()
-                    else:
-                        blk[name] = run_short_config(bp, lib, name, args, gens_by_cap)
+                    gens.release_scratch()
+                    lat = {"call_shape": LATENCY_SHAPE}
+                    lat["c4"] = run_latency(bp, lib, "c4", wl.vsmt4(bp, None, 32, 64, 64, 0), gens, "c4_vsmt4_d32_x2024")
+                    gens.release_scratch()
+                    g1 = bp.Gens(128)
+                    lat["c1"] = run_latency(bp, lib, "c1", wl.bound_check64(64), g1, "c1_bound_check64_x4096")
+                    g1.close()
+                    if n_cpu > 0:   # the CPU port on the single-prover configuration (BASELINE config 1), one thread
+                        cb1, _ = cpu_baseline(wl.bound_check64(64), 32, 1)
+                        st1c = (cb1.get("single_thread") or {}).get("value")
+                        if st1c:
+                            lat["c1"]["cpu_port_ms_per_proof"] = 1e3 / st1c
+                            lat["c1"]["speedup_b1_vs_cpu_port_1_thread"] = (1e3 / st1c) / lat["c1"]["b1"]["ms_per_proof"]
+                    cb = out.get("cpu_baseline") or {}
+                    st1 = (cb.get("single_thread") or {}).get("value")
+                    if st1:
+                        lat["c4"]["cpu_port_ms_per_proof"] = 1e3 / st1
+                        lat["c4"]["speedup_b1_vs_cpu_port_1_thread"] = (1e3 / st1) / lat["c4"]["b1"]["ms_per_proof"]
+                    out["latency"] = lat
                 except Exception as e:  # pragma: no cover
-                    blk[name] = {"error": repr(e)}
-                blk[name]["wall_s"] = time.time() - t1
-            out["configs"] = blk
-            for name, row in blk.items():   # the literal reference tests of the as-shipped depths belong to the `latency` block
-                if isinstance(row, dict) and "latency" in row and isinstance(out.get("latency"), dict):
-                    out["latency"][CONFIGS[name]["latency_row"]] = row.pop("latency")
+                    out["latency"] = {"error": repr(e)}
+            # the other BASELINE configurations, each a short run of its own with the library's defaults (1-GPU runs only)
+            which = args.configs
+            if which == "default":
+                which = "c4,c3,c1,c2,c5,vsmt4_d128,vsmt2_d253" if (args.config == "c4" and args.depth == 32 and not options and world == 1) else "none"
+            if which != "none" and world == 1:
+                circ.close()
+                gens_by_cap = {N: gens}
+                blk = {}
+                for name in [x for x in which.split(",") if x]:
+                    t1 = time.time()
+                    try:
+                        if name == args.config and cfg.get("fixture") and "fixture_build" in cfg and N in gens_by_cap:
+                            # the headline itself: its throughput is `value`; here EVERY proof of the fixture batch against the oracle digests
+                            fw = cfg["fixture_build"](bp)
+                            fcirc = bp.CompiledGadget(fw["gadget"], fw["ip"], fw["sp"])
+                            fproofs, _ = bp.prove_batch_raw(gens, fcirc, fw["label"], fw["values"], fw["blindings"], fw["seeds"], fw["B"])
+                            blk[name] = {"metric": metric, "value": value, "unit": "proofs/s", "note": "the headline of this line", "parity": fixture_parity(cfg["fixture"], fw, fproofs, fcirc.proof_len)}
+                            fcirc.close()
+                        else:
+                            blk[name] = run_short_config(bp, lib, name, args, gens_by_cap)
+                    except Exception as e:  # pragma: no cover
+                        blk[name] = {"error": repr(e)}
+                    blk[name]["wall_s"] = time.time() - t1
+                out["configs"] = blk
+                for name, row in blk.items():   # the literal reference tests of the as-shipped depths belong to the `latency` block
+                    if isinstance(row, dict) and "latency" in row and isinstance(out.get("latency"), dict):
+                        out["latency"][CONFIGS[name]["latency_row"]] = row.pop("latency")
         result_line = json.dumps(out)
     else:
         result_line = None

@@ -37,3 +37,28 @@ def test_workloads_are_the_ones_the_digest_fixture_pins():
     # C1: the single-prover latency case of bench.py proves the first witnesses of the throughput batch
     assert fc.input_digest(wl.bound_check64(4096)) == fx["c1_bound_check64_x4096"]["inputs_sha256"]
     assert wl.slice_proof(wl.bound_check64(64), 63) == wl.slice_proof(wl.bound_check64(4096), 63)
+
+
+def test_dump_outputs_writes_the_last_step(tmp_path):
+    """--dump-outputs: the proof and commitment bytes of the LAST timed step as float32, every row while they fit in
+    bench.DUMP_BYTES_MAX, else the same seeded sample of rows on every run"""
+    import numpy as np
+    import bench
+    B, steps, plen, m = 64, 3, 1377, 100
+    rng = np.random.default_rng(1)
+    P, C = bytearray(rng.bytes(steps * B * plen)), bytearray(rng.bytes(steps * B * m * 32))
+    bench.dump_outputs(str(tmp_path / "a"), P, C, B, steps, plen, m)
+    p, c, i = (np.load(str(tmp_path / "a" / f)) for f in ("proofs.npy", "commitments.npy", "proof_index.npy"))
+    assert p.dtype == c.dtype == np.float32 and i.dtype == np.float64
+    assert p.shape == (B, plen) and c.shape == (B, m, 32) and list(i) == list(range((steps - 1) * B, steps * B))
+    first = (steps - 1) * B
+    assert bytes(p.astype(np.uint8)) == bytes(P[first * plen:])
+    assert bytes(c.astype(np.uint8)) == bytes(C[first * m * 32:])
+    B, m = 4096, 388   # 4096 x (1377 + 388 x 32) bytes would pass the bound as float32
+    P, C = bytearray(steps * B * plen), bytearray(steps * B * m * 32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), P, C, B, steps, plen, m, "_rank1")
+    total = sum(f.stat().st_size for f in (tmp_path / "b").iterdir())
+    assert total <= 64 * 10**6 and np.load(str(tmp_path / "b" / "proofs_rank1.npy")).shape[0] < B
+    ib, ic = np.load(str(tmp_path / "b" / "proof_index_rank1.npy")), np.load(str(tmp_path / "c" / "proof_index_rank1.npy"))
+    assert np.array_equal(ib, ic) and np.all(np.diff(ib) > 0) and ib[0] >= (steps - 1) * B

@@ -3,7 +3,7 @@
 flight): steady-state period between consecutive K_assemble launches, how busy the stream is, and the time every kernel
 takes per batch on it; plus the front kernels (TranscriptRng chain, witness synthesis) and the MSM launches of one batch,
 each with the share of its duration a front kernel of the NEXT batch was running.
-  rocprofv3 --kernel-trace -d DIR -o out -- python bench.py --steps 6 --warmup 1 --cpu-proofs 0 ; trace_perjob.py DIR [rows]"""
+  rocprofv3 --kernel-trace -d DIR -o out -- python bench.py --full --steps 6 --warmup 1 --cpu-proofs 0 ; trace_perjob.py DIR [rows]"""
 import sqlite3, sys, glob, collections
 db = sorted(glob.glob(sys.argv[1] + "/**/*.db", recursive=True))[-1]
 con = sqlite3.connect(db)
