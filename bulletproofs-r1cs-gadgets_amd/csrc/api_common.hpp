@@ -50,6 +50,7 @@ struct BpOpts {
     std::atomic<int> job_proofs{0};        // proofs per device job of bpr1cs_prove_batch (0: from the free memory)
     std::atomic<int> jobs_in_flight{2};
     std::atomic<int> host_chain{-1};       // jobs of up to this many proofs run their TranscriptRng chains on host threads (-1: 4 per usable CPU; 0: never)
+    std::atomic<int> host_chain_share{-1}; // percent of a larger job's chains streamed from host threads (-1: 100 for a job that follows another of its call, with AVX-512)
     int window_bits = 0;                   // creation only (0: from the free memory)
 };
 // -> false for an unknown option (or a creation-only one after creation)
@@ -64,6 +65,7 @@ static bool opt_apply(BpOpts& o, int option, int value, bool creating) {
         case BPR1CS_OPT_JOB_PROOFS: o.job_proofs = value < 0 ? 0 : value; return true;
         case BPR1CS_OPT_JOBS_IN_FLIGHT: o.jobs_in_flight = (value == 1) ? 1 : 2; return true;
         case BPR1CS_OPT_HOST_CHAIN_PROOFS: o.host_chain = value < 0 ? -1 : value; return true;
+        case BPR1CS_OPT_HOST_CHAIN_SHARE: o.host_chain_share = value < 0 ? -1 : (value > 100 ? 100 : value); return true;
         case BPR1CS_OPT_WINDOW_BITS:
             if (!creating) return false;
             o.window_bits = value <= 0 ? 0 : (value < 4 ? 4 : (value > 15 ? 15 : value));   // (digits travel as sign + 15-bit magnitude: |d| <= 2^14 at W = 15)
@@ -196,6 +198,7 @@ struct bpr1cs_circuit {
         uint32_t hs_W = 0, hs_cap = 0;
         uint32_t job_proofs = 0;   // proofs per device job chosen for (this circuit, this handle) by the first bpr1cs_prove_batch: kept for the later ones ...
         uint32_t job_epoch = 0;    // ... while the handle's sizing_epoch is the one it was chosen under
+        double msm_ms_per_proof = 0;   // heavy-stream multiscalar time per proof of the last bpr1cs_prove_batch (the default host share of its chains)
         uint64_t sz_avail = 0, sz_per_proof = 0, sz_fixed = 0;   // what that choice was made from (bpr1cs_prove_stats.sizing_*)
     };
     mutable std::mutex mt_mu;

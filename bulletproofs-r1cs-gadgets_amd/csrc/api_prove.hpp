@@ -27,6 +27,10 @@ struct bpr1cs_job {
     size_t h_raw_bytes = 0;
     strobe* h_tr0 = nullptr;
     bool host_chain = false;
+    // a larger job's split (BPR1CS_OPT_HOST_CHAIN_SHARE): the chains of its first Bh proofs are streamed from host threads through a
+    // pinned ring (h_raw) after their RNG states (h_tr0) are read back at ev_head; the rest run in k_rng_stream
+    uint32_t Bh = 0;
+    dev_event_t ev_head{};
 };
 // pinned staging buffers are cached: hipHostFree (like hipFree) synchronises the whole device, which
 // would serialise the in-flight jobs
@@ -99,12 +103,13 @@ static void job_release(bpr1cs_job* job) {
     for (auto e : job->pt.ev) (void)hipEventDestroy(e);
     job->pt.ev.clear();
 #endif
-    dev_event_t* evs[5] = {&job->ev_in, &job->ev_rng, &job->ev_wit, &job->ev_done, &job->ev_tail};
+    dev_event_t* evs[6] = {&job->ev_in, &job->ev_rng, &job->ev_wit, &job->ev_done, &job->ev_tail, &job->ev_head};
     for (auto e : evs) dev_event_destroy(e);
     for (void* p : job->deferred) dev_free_now(p);
     job->deferred.clear();
     if (job->h_raw) host_wipe(job->h_raw, job->h_raw_bytes);
     if (job->h_in) host_wipe(job->h_in, job->h_in_bytes);
+    if (job->h_tr0 && job->Bh) host_wipe(job->h_tr0, (size_t)job->Bh * sizeof(strobe));
     host_stage_free(job->h_in);
     host_stage_free(job->h_raw);
     host_stage_free(job->h_V);
@@ -155,7 +160,7 @@ static int prove_job_fail(const bpr1cs_gens* g, bpr1cs_job* job, uint32_t slot, 
 // Transcript::new(label) gives) or n_init = batch (the caller's own); want_tr: read the final transcript states back.
 static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const strobe* init, size_t n_init, bool want_tr,
                            const uint8_t* values, const uint8_t* v_blindings, const uint8_t* rng_seeds,
-                           const uint8_t* wires, size_t batch, bpr1cs_job** job_out, const uint8_t* ext_draws = nullptr) {
+                           const uint8_t* wires, size_t batch, bpr1cs_job** job_out, const uint8_t* ext_draws = nullptr, int auto_share = 0) {
     // ext_draws (bpr1cs_prove_batch_draws): the caller has appended Prover::new's and commit's transcript messages and "m" itself - `init` holds
     // one transcript per proof in that state - and has run the proof's TranscriptRng: batch x (2n + 8) raw 64-byte draws
     if (!g || !c || !init || (!rng_seeds && !ext_draws) || !job_out || batch == 0 || (n_init != 1 && n_init != batch)) return BPR1CS_ERR_INVALID_ARGUMENT;
@@ -265,6 +270,21 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     const bool ext = ext_draws != nullptr;
     const bool host_chain = !ext && (o_hc < 0 ? B <= 4u * host_cpu_budget() : B <= (uint32_t)o_hc);
     job->host_chain = host_chain;
+    // The split (BPR1CS_OPT_HOST_CHAIN_SHARE): in a job that follows another job of its call, the chains run beside that job's
+    // sums - k_rng_stream took ~9 % of the GPU's kernel time beside them and slowed the A_I / S launches by 80 ms a job -
+    // while the host's cores sit idle.  auto_share: what bpr1cs_prove_batch chose for this job (host_chain_share_auto: the part the
+    // host's budget - 1 workers hash within the heavy stream's time per job; 0 for the first job of a call).  No split without a
+    // worker: the calling thread only hands the chunks over.
+    uint32_t Bh = 0;
+    const unsigned chain_workers = host_cpu_budget() - 1;
+#if !defined(BPR1CS_HOSTSIM)
+    if (!ext && !host_chain && chain_workers > 0) {
+        const int o_share = g->opts.host_chain_share.load();
+        const int share = o_share >= 0 ? o_share : std::max(0, std::min(100, auto_share));
+        Bh = (uint32_t)(((uint64_t)B * (uint32_t)share + 50) / 100);
+    }
+#endif
+    job->Bh = Bh;
     {
         ArenaScope sh(shared ? &g->shared_front : &g->front[slot], shared);
         W.alloc((size_t)5 * n * B + 1);
@@ -311,16 +331,27 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
         // parallel.  Hidden behind the sums of the job before this one when a batch is cut into jobs.
         rng.alloc(B);
         launch_transcript(B, K_transcript_init{d_init.p, init_stride, Vcomp.p, vbl_raw.p, d_seeds.p, tr.p, blind.p, sL, sR, rng.p, B, m, n}, sl);
+        if (Bh) {   // the host's share: its RNG states go back now (before the device chain is queued on this stream)
+            job->h_tr0 = (strobe*)host_stage_alloc((size_t)Bh * sizeof(strobe));
+            dev_d2h_async(job->h_tr0, rng.p, (size_t)Bh * sizeof(strobe), sl);
+            dev_event_create(&job->ev_head);
+            dev_event_record(job->ev_head, sl);
+        }
         if (shared) dev_stream_wait(sl, g->rng_free_ev);   // the job before has reduced (and wiped) its raw output
-        hipLaunchKernelGGL(k_rng_stream, dim3((B + 1) / 2), dim3(64), 0, sl, rng.p, rng_raw.p, rng_err.p, B, draws);
-        HIPCHK(hipGetLastError());
-        if (shared) dev_stream_wait(sl, g->w_free_ev);     // s_L / s_R live in W: the job before is past its l(x), r(x)
-        launch((uint64_t)draws * B, K_rng_reduce{rng_raw.p, blind.p, sL, sR, B, n, 0u}, sl);
-        dev_zero(rng_raw.p, rng_raw.bytes(), sl);  // raw blinding material
-        dev_zero(rng.p, rng.bytes(), sl);
-        if (shared) dev_event_record(g->rng_free_ev, sl);
+        // split: [2n+7][Bh][8] words of the host's proofs first, then [2n+7][B - Bh][8] of the device's (each part contiguous per draw)
+        if (Bh < B) {
+            hipLaunchKernelGGL(k_rng_stream, dim3((B - Bh + 1) / 2), dim3(64), 0, sl, rng.p + Bh, rng_raw.p + (size_t)draws * Bh * 8, rng_err.p, B - Bh, draws);
+            HIPCHK(hipGetLastError());
+        }
+        if (!Bh) {
+            if (shared) dev_stream_wait(sl, g->w_free_ev);     // s_L / s_R live in W: the job before is past its l(x), r(x)
+            launch((uint64_t)draws * B, K_rng_reduce{rng_raw.p, blind.p, sL, sR, B, n, 0u}, sl);
+            dev_zero(rng_raw.p, rng_raw.bytes(), sl);  // raw blinding material
+            dev_zero(rng.p, rng.bytes(), sl);
+            if (shared) dev_event_record(g->rng_free_ev, sl);
+        }
 #endif
-        dev_event_record(job->ev_rng, sl);
+        if (!Bh) dev_event_record(job->ev_rng, sl);
     }
 
     if (host_chain) {
@@ -375,7 +406,45 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
 #endif
     }
     // the chains' end of the hand-over: called where the heavy stream is about to wait for the draws (in front of S1)
+    // the split's host part, where the heavy stream is about to wait for the draws (in front of S1): the chains stream in chunks of
+    // 256 draws through a ring of 4 pinned slots (64 MiB each at 4096 proofs) on the job's witness stream - a copy engine's work, the
+    // heavy stream never waits for a copy - into the host part of rng_raw; both parts are reduced on the front stream after it
+    auto finish_split = [&]() {
+        if (!Bh) return;
+        const uint32_t Dc = 256, R = 4;
+        const dev_stream_t su = job->st3;
+        if (!dev_event_sync(job->ev_head)) throw DevError{BPR1CS_ERR_DEVICE};
+        job->h_raw_bytes = (size_t)R * Dc * Bh * 64;
+        job->h_raw = (uint64_t*)host_stage_alloc(job->h_raw_bytes);
+        if (shared) dev_stream_wait(su, g->rng_free_ev);
+        dev_event_t ev_slot[R] = {};
+        for (uint32_t r = 0; r < R; r++) dev_event_create(&ev_slot[r]);
+        struct Events { dev_event_t* e; uint32_t n; ~Events() { for (uint32_t r = 0; r < n; r++) dev_event_destroy(&e[r]); } } evs_guard{ev_slot, R};
+        uint64_t* raw_h = rng_raw.p;
+        DBG_JOB("begin: %u host chain(s) of %u streamed (%.4f us per permutation and worker)", Bh, B, host_chain_us_per_perm());
+        double busy_us = 0;
+        const bool ok = host_chains_stream(job->h_tr0, Bh, draws, Dc, R, job->h_raw, chain_workers,
+            [&](uint32_t, uint32_t slot, uint32_t d0, uint32_t nd) {
+                dev_h2d_async(raw_h + (size_t)d0 * Bh * 8, job->h_raw + (size_t)slot * Dc * Bh * 8, (size_t)nd * Bh * 64, su);
+                dev_event_record(ev_slot[slot], su);
+            },
+            [&](uint32_t slot) { if (!dev_event_sync(ev_slot[slot])) throw DevError{BPR1CS_ERR_DEVICE}; }, chain8_select(), &busy_us);
+        if (ok && busy_us > 0) host_chain_rate_cell().store(busy_us / ((double)Bh * draws));   // (the next jobs' share is sized from it)
+        host_wipe(job->h_tr0, (size_t)Bh * sizeof(strobe));   // (the RNG states: key material)
+        if (!ok) throw DevError{BPR1CS_ERR_INVALID_ARGUMENT};   // (not the steady STROBE state - k_rng_stream refuses it alike)
+        DBG_JOB("begin: host chain(s) hashed");
+        dev_event_record(job->ev_head, su);
+        dev_stream_wait(sl, job->ev_head);
+        if (shared) dev_stream_wait(sl, g->w_free_ev);
+        launch((uint64_t)draws * Bh, K_rng_reduce{raw_h, blind.p, sL, sR, B, n, 0u, Bh, 0u}, sl);
+        if (Bh < B) launch((uint64_t)draws * (B - Bh), K_rng_reduce{raw_h + (size_t)draws * Bh * 8, blind.p, sL, sR, B, n, 0u, B - Bh, Bh}, sl);
+        dev_zero(rng_raw.p, rng_raw.bytes(), sl);
+        dev_zero(rng.p, rng.bytes(), sl);
+        if (shared) dev_event_record(g->rng_free_ev, sl);
+        dev_event_record(job->ev_rng, sl);
+    };
     auto finish_host_chains = [&]() {
+        finish_split();
         if (!host_chain) return;
         chains.wait();
         DBG_JOB("begin: host chain(s) done");
@@ -644,6 +713,7 @@ static int prove_job_end(bpr1cs_job* job, uint8_t* proofs_out, uint8_t* commitme
             for (int i = 0; i < 6; i++) acc->phase_ms[i] += ph[i];
             acc->msm_ms += job->msm.ms; acc->msm_launches += job->msm.launches; acc->msm_terms += job->msm.terms; acc->msm_adds += job->msm.adds;
             if (job->host_chain) acc->host_chains += job->B;
+            else acc->host_chains += job->Bh;
         }
     }
     job_release(job);
@@ -736,15 +806,35 @@ static int prove_batch_impl(const bpr1cs_gens* g, const bpr1cs_circuit* c, const
     struct Pending { bpr1cs_job* job; size_t first; };
     std::vector<Pending> fl;
     int rc = BPR1CS_OK;
+    size_t ended = 0;   // proofs of the jobs ended so far (acc.msm_ms is theirs)
     auto finish_oldest = [&]() {
         Pending p = fl.front();
         fl.erase(fl.begin());
+        ended += p.job->B;
         int e = prove_job_end(p.job, proofs_out + p.first * plen, commitments_out ? commitments_out + p.first * m * 32 : nullptr,
                               tr_out ? tr_out + p.first : nullptr, &acc);
         if (e != BPR1CS_OK && rc == BPR1CS_OK) rc = e;
     };
     size_t done = 0;
     bool retried = false;
+    // the default host share of the next job (BPR1CS_OPT_HOST_CHAIN_SHARE = -1, csrc/host_chain.hpp host_chain_share_auto): none for the
+    // first job of the call; for a job that follows another, what the host hashes in 3/4 of the heavy stream's time for the job before
+    // it - its multiscalar time per proof measured so far in this call, else in the last call of this circuit on this handle, else the
+    // device chain's own length (2.5 us per permutation: the job before runs it in front of its sums)
+    double prior_ms_per_proof = 0;
+    {
+        std::lock_guard<std::mutex> lk(c->mt_mu);
+        auto it = c->mt.find(g);
+        if (it != c->mt.end()) prior_ms_per_proof = it->second->msm_ms_per_proof;
+    }
+    auto auto_share = [&](size_t take) -> int {
+        if (fl.empty() || ext_draws || g->opts.host_chain_share.load() >= 0) return 0;
+        const uint32_t draws = 2 * c->n + 7;
+        const size_t before = fl.back().job->B;
+        const double per_proof = ended && acc.msm_ms > 0 ? acc.msm_ms / ended : prior_ms_per_proof;
+        const double deadline_ms = per_proof > 0 ? per_proof * before : draws * 2.5e-3;
+        return host_chain_share_auto(chain8_select() != chain8_advance_scalar, take, draws, host_cpu_budget() - 1, host_chain_us_per_perm(), deadline_ms);
+    };
     // test knob (tests/test_hostsim.py): BPR1CS_TEST_FAIL_JOBS=k makes the first k job submissions of this call report "out of
     // memory", so that the drain / hand back / retry / halve path below runs without a device that is actually full
 #if defined(BPR1CS_HOSTSIM)
@@ -764,7 +854,7 @@ static int prove_batch_impl(const bpr1cs_gens* g, const bpr1cs_circuit* c, const
         else e = prove_job_begin(g, c, n_init == 1 ? init : init + done, n_init == 1 ? 1 : take, tr_out != nullptr,
                                  values ? values + done * m * 32 : nullptr, v_blindings ? v_blindings + done * m * 32 : nullptr,
                                  rng_seeds ? rng_seeds + done * 32 : nullptr, wires ? wires + done * wn * 32 : nullptr, take, &job,
-                                 ext_draws ? ext_draws + done * (2 * (size_t)c->n + 8) * 64 : nullptr);
+                                 ext_draws ? ext_draws + done * (2 * (size_t)c->n + 8) * 64 : nullptr, auto_share(take));
         if (e == BPR1CS_ERR_OUT_OF_MEMORY && (take > 64 || !retried)) {
             // out of memory: let the jobs in flight finish and hand the scratch back (arenas sized for the smaller jobs of an
             // earlier call sit next to the blocks that replace them until their last user has drained) - then the same job once
@@ -794,6 +884,12 @@ static int prove_batch_impl(const bpr1cs_gens* g, const bpr1cs_circuit* c, const
         if ((int)fl.size() >= depth) finish_oldest();
     }
     while (!fl.empty()) finish_oldest();
+    if (rc == BPR1CS_OK && ended && acc.msm_ms > 0) {
+        std::lock_guard<std::mutex> lk(c->mt_mu);
+        bpr1cs_circuit::MergedTab*& mt = c->mt[g];
+        if (!mt) mt = new bpr1cs_circuit::MergedTab();
+        mt->msm_ms_per_proof = acc.msm_ms / ended;
+    }
     tl_last_stats() = acc;
     return rc;
 }

@@ -288,16 +288,21 @@ struct K_transcript_init {
 // raw 64-byte RNG outputs -> Montgomery scalars in their slots.  lead = 0: draws d >= 1 of the stream as k_rng_stream writes them,
 // [2n+7][B][8] words, gid = d*B + b.  lead = 1: all 2n+8 draws of chains that ran on host threads (csrc/host_chain.hpp), one proof's
 // draws after the other's - [B][2n+8][8] words, gid = b*(2n+8) + d: a thread per proof writes its own run of cache lines
+// (lead = 0 with Bc != 0: the stream of the Bc proofs b0 .. b0 + Bc - 1 only, [2n+7][Bc][8] words - a job whose chains are split
+// between host threads and k_rng_stream keeps the two parts apart)
 struct K_rng_reduce {  // [i_bl,] o_bl, s_bl, s_L[n], s_R[n], t1 t3 t4 t5 t6 blindings
     const uint64_t* raw;
     sc* blind;
     sc* sL;
     sc* sR;
     uint32_t B, n, lead;
+    uint32_t Bc = 0, b0 = 0;
     HD void operator()(uint32_t g) const {
         uint32_t d, b;
         if (lead) {
             b = g / (2 * n + 8); d = g % (2 * n + 8);
+        } else if (Bc) {
+            d = g / Bc; b = b0 + g % Bc;
         } else {
             d = g / B; b = g % B;
         }

@@ -170,6 +170,16 @@ int bpr1cs_gens_table_info(const bpr1cs_gens* g, uint32_t* window_bits, uint32_t
                                          thread (public bytes only; 0 keeps them on the device).  Hashing, and for the verifier the
                                          reduction and inversion of its public challenges, only - no group arithmetic, and no arithmetic
                                          on a secret, ever runs on the host */
+#define BPR1CS_OPT_HOST_CHAIN_SHARE 10 /* measuring option: percent (0..100) of a large job's proofs whose TranscriptRng chains run on host threads,
+                                         eight proofs per AVX-512 register set, streamed to the device in chunks of draws while the rest run
+                                         in k_rng_stream.  Default (-1), per job of bpr1cs_prove_batch: none for the first job of a call (it
+                                         has nothing to hide behind), none without AVX-512 or with fewer than 2 worker threads (the process
+                                         may use budget - 1 of its usable CPUs: affinity mask, cgroup quota); otherwise the share the workers
+                                         hash in 3/4 of the heavy stream's time per job measured so far in the call (its multiscalar
+                                         launches; before any job has ended, the length of the device chain), at the rate the workers last
+                                         measured - e.g. 100 % of a 4096-proof depth-32 job on 15 workers, ~55 % on 3.  A pinned share is
+                                         honoured whenever there is a worker.  Jobs that BPR1CS_OPT_HOST_CHAIN_PROOFS puts on the host whole
+                                         are not affected */
 #define BPR1CS_OPT_WINDOW_BITS 16     /* creation only: signed window width W (4..15) of the fixed-base tables.  A term costs
                                          ceil(253/W) mixed additions; table bytes = (2+2*cap) * ceil(253/W) * (2^(W-1)+1) * 128
                                          (W=8: 35 GB, W=11: 198 GB at capacity 32768).  Default 0 = the widest W <= 15 whose tables fit in

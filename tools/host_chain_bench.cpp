@@ -27,5 +27,19 @@ int main(int argc, char** argv) {
             if (rep) printf("%2u threads x 1 chain of %zu draws: %.2f ms wall, %.3f us per permutation per chain (%016llx)\n", T, draws, us / 1e3, us / draws, (unsigned long long)raw[8 * 5]);
         }
     }
+    // the eight-way chain (csrc/host_chain.hpp chain8_*): one thread, eight steady-state chains, scalar fallback and AVX-512
+    for (int avx = 0; avx < 2; avx++) {
+        const chain8_fn fn = chain8_select(avx != 0);
+        Chain8 g;
+        for (int k = 0; k < 25; k++)
+            for (int p = 0; p < 8; p++) g.st[k][p] = 0x9e3779b97f4a7c15ull * (uint64_t)(25 * p + k + 1);
+        const uint32_t D = 8192;
+        std::vector<uint64_t> out((size_t)D * 64);
+        fn(g, 8, 512, out.data(), 8, 64);
+        auto t0 = std::chrono::steady_clock::now();
+        fn(g, 8, D, out.data(), 8, 64);
+        const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+        printf("1 thread x 8 chains (%s): %.4f us per permutation per chain\n", fn == chain8_advance_scalar ? "scalar fallback" : "avx512", us / D / 8);
+    }
     return 0;
 }
