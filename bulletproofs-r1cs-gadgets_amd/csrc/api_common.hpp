@@ -12,6 +12,7 @@
 #include "dev.hpp"
 #include "kernels.hpp"
 #include "msm_kernel.hpp"
+#include "msm_ct_kernel.hpp"
 #if !defined(BPR1CS_HOSTSIM)
 #include "kernels_hip.hpp"
 #endif
@@ -52,6 +53,7 @@ struct BpOpts {
     std::atomic<int> host_chain{-1};       // jobs of up to this many proofs run their TranscriptRng chains on host threads (-1: 4 per usable CPU; 0: never)
     std::atomic<int> host_chain_share{-1}; // percent of a larger job's chains streamed from host threads (-1: 100 for a job that follows another of its call, with AVX-512)
     int window_bits = 0;                   // creation only (0: from the free memory)
+    int secret_independent = 0;            // creation only: 1 = the commit phase runs through k_msm_fixed_ct over a narrow table set of its own
 };
 // -> false for an unknown option (or a creation-only one after creation)
 static bool opt_apply(BpOpts& o, int option, int value, bool creating) {
@@ -69,6 +71,10 @@ static bool opt_apply(BpOpts& o, int option, int value, bool creating) {
         case BPR1CS_OPT_WINDOW_BITS:
             if (!creating) return false;
             o.window_bits = value <= 0 ? 0 : (value < 4 ? 4 : (value > 15 ? 15 : value));   // (digits travel as sign + 15-bit magnitude: |d| <= 2^14 at W = 15)
+            return true;
+        case BPR1CS_OPT_SECRET_INDEPENDENT:
+            if (!creating || (value != 0 && value != 1)) return false;   // (owns memory the choice of W and the job-size model must see from the start)
+            o.secret_independent = value;
             return true;
         default: return false;
     }
@@ -143,6 +149,11 @@ struct bpr1cs_gens {
     TabCfg tc{};             // fixed-base table geometry (window bits chosen at creation)
     DevBuf<ge> pts;          // [2 + 2cap] : B, B~, G.., H..
     DevBuf<uint8_t> tab;     // [(2+2cap) * windows * row] slots of tc.stride bytes
+    // BPR1CS_OPT_SECRET_INDEPENDENT: a second set for the same bases at the narrow window MSM_CT_W, read row by row by k_msm_fixed_ct
+    // (empty otherwise).  The wide set above stays what the inner-product argument and the verifier use.
+    TabCfg tc_ct{};
+    DevBuf<uint8_t> tab_ct;
+    bool ct() const { return tab_ct.p != nullptr; }
     std::vector<uint8_t> comp;  // compressed, host copy
     dev_stream_t stream{};   // setup / synchronous helpers
     // two stream pairs so that two prove jobs can be in flight (cross-batch pipelining);

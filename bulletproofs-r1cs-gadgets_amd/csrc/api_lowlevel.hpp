@@ -226,6 +226,18 @@ extern "C" int bpr1cs_msm_fixed(const bpr1cs_gens* g, const uint32_t* bases, siz
     if (terms == 2 && bases[0] == 0 && bases[1] == 1) {
         // pc_gens.commit(v, blinding) = v*B + blinding*B_blinding - what Prover::commit calls once per committed value (reference
         // src/gadget_vsmt_4.rs:393-410: 100 calls for one depth-32 proof): one upload, ONE kernel (the prover's own K_commit_v), one read-back
+        if (g->ct()) {   // secret-independent handle: k_msm_fixed_ct over the rows of B and B~, whatever the batch
+            std::vector<sc> h((size_t)2 * B);
+            for (uint32_t b = 0; b < B; b++) { h[b] = sc_load_raw(scalars + 64 * (size_t)b); h[(size_t)B + b] = sc_load_raw(scalars + 64 * (size_t)b + 32); }
+            DevBuf<sc> d((size_t)2 * B);
+            DevBuf<uint8_t> d_out((size_t)B * 32);
+            dev_h2d_async(d.p, h.data(), h.size() * sizeof(sc), st);
+            run_commit_ct(g, d.p, d.p + B, MSM_CANONICAL, B, d_out.p, B, 0, st, nullptr);
+            dev_zero(d.p, d.bytes(), st);   // value and blinding are secrets
+            dev_d2h(out, d_out.p, (size_t)B * 32, st);
+            host_wipe(h.data(), h.size() * sizeof(sc));
+            return BPR1CS_OK;
+        }
 #if !defined(BPR1CS_HOSTSIM)
         if (B == 1) {
             // ONE commitment per call - the reference's own shape (100 calls in a row for a depth-32 proof, each result needed at

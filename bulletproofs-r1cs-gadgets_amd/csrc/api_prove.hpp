@@ -248,10 +248,13 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
 
     DBG_JOB("begin: inputs uploaded");
     // ---- P1: V commitments, transcript, RNG stream
+    MSM_TRACE_F2_MUTE(0);
     DevBuf<uint8_t> Vcomp((size_t)B * m * 32 + 1);
     if (ext_draws) {
         dev_zero(Vcomp.p, Vcomp.bytes(), sl);   // (the caller has made the commitments - they are in its transcripts - and this call returns none)
     } else
+    if (g->ct()) run_commit_ct(g, v_raw.p, vbl_raw.p, MSM_CANONICAL, m * B, Vcomp.p, B, m, sl, nullptr);   // (whatever the count: one kernel covers the contract)
+    else
 #if !defined(BPR1CS_HOSTSIM)
     if ((uint64_t)m * B <= 256 && m * B > 0) {   // a handful of commitments in front of the transcript chain: a wavefront each (180 -> ~25 us for one proof)
         hipLaunchKernelGGL(k_commit_wave, dim3(m * B), dim3(64), 0, sl, (const uint8_t*)g->tab.p, g->tc, (const sc*)v_raw.p, (const sc*)vbl_raw.p, Vcomp.p, B, m);
@@ -483,7 +486,8 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
         MsmPlan planO, planO1{0, 0}, planS;
         const ge* ones_pt = nullptr;
         K_msm_finish finI{g->tab.p, g->tc, nullptr, blind.p + 0 * (size_t)B, nullptr, AOS.p + 0 * (size_t)B * 32, B, 0, 1};
-        if (!wires && T3) {
+        const bool ct = g->ct();   // secret-independent handle: plain n-term sums through k_msm_fixed_ct, for compiled circuits as for host wires
+        if (!wires && T3 && !ct) {
             // A_I1 with the repeated S-box wires merged: 2 terms per S-box instead of 5 (see K_merge_points).  The merged
             // tables belong to (circuit, generator handle); the first job that needs them builds them on the heavy stream.
             const uint8_t* mtab = nullptr;
@@ -527,13 +531,31 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
             finI.nchunks_b = plan2.nchunks;
         } else {
             MsmReq rq[2] = {{seg(aL, baseG), seg(aR, baseH), &partial, &plan, nullptr}, {seg(aO, baseG), none, &partialO, &planO, nullptr}};
-            run_msm_multi(g, rq, 2, B, st, stats);
+            run_msm_multi(g, rq, 2, B, st, stats, nullptr, ct);
             finI.partial = partial.p;
             finI.nchunks = plan.nchunks;
         }
         finish_host_chains();
         dev_stream_wait(st, job->ev_rng);  // the chain's draws (blindings, s_L, s_R), the transcript after the V's
         pt.mark(st);
+        if (ct) {
+            // S1 and the three blinding terms i_bl B~, o_bl B~, s_bl B~ as ordinary terms of the same kernel, one launch; the finishes
+            // only add chunk sums and compress (a lane per proof whatever the batch)
+            DevBuf<ge> pbI, pbO, pbS;
+            MsmPlan plI, plO, plS;
+            auto bl = [&](uint32_t k) { return MsmSeg{blind.p + (size_t)k * B, 1, 1, 1, 0, 1, MSM_MONT}; };
+            MsmReq rq[4] = {{seg(sL, baseG), seg(sR, baseH), &partialS, &planS, nullptr}, {bl(0), none, &pbI, &plI, nullptr},
+                            {bl(1), none, &pbO, &plO, nullptr}, {bl(2), none, &pbS, &plS, nullptr}};
+            run_msm_multi(g, rq, 4, B, st, stats, nullptr, true);
+            finI.extra = nullptr; finI.partial_b = pbI.p; finI.nchunks_b = plI.nchunks;
+            K_msm_finish finO{g->tab.p, g->tc, partialO.p, nullptr, nullptr, AOS.p + 1 * (size_t)B * 32, B, planO.nchunks, 1};
+            finO.partial_b = pbO.p; finO.nchunks_b = plO.nchunks;
+            K_msm_finish finS{g->tab.p, g->tc, partialS.p, nullptr, nullptr, AOS.p + 2 * (size_t)B * 32, B, planS.nchunks, 1};
+            finS.partial_b = pbS.p; finS.nchunks_b = plS.nchunks;
+            launch(B, finI, st);
+            launch(B, finO, st);
+            launch(B, finS, st);
+        } else {
         K_msm_finish finO{g->tab.p, g->tc, partialO.p, blind.p + 1 * (size_t)B, nullptr, AOS.p + 1 * (size_t)B * 32, B, planO.nchunks, 1};
         if (ones_pt) { finO.shared_pt = ones_pt; finO.partial_b = partialO1.p; finO.nchunks_b = planO1.nchunks; }
         if (B <= SMALL_JOB_PROOFS) {
@@ -545,6 +567,7 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
             launch_finish(finO, B, st);
             run_msm(g, seg(sL, baseG), seg(sR, baseH), B, partial, plan, st, stats);
             launch_finish(K_msm_finish{g->tab.p, g->tc, partial.p, blind.p + 2 * (size_t)B, nullptr, AOS.p + 2 * (size_t)B * 32, B, plan.nchunks, 1}, B, st);
+        }
         }
     }
     pt.mark(st);
@@ -582,6 +605,12 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     DevBuf<sc> tpart((size_t)6 * TC * B), tco((size_t)6 * B);
     launch((uint64_t)TC * B, K_tcoef_partial{W.p, wvec.p, plo.p, phi.p, tpart.p, B, H, n, tchunk, TC}, st);
     launch_sum_partials((uint64_t)6 * B, K_sum_partials{tpart.p, tco.p, B, TC}, st);
+    if (g->ct()) {
+        DevBuf<sc> tsc((size_t)10 * B);
+        launch((uint64_t)5 * B, K_ct_gather_T{tco.p, blind.p, tsc.p, B}, st);
+        run_commit_ct(g, tsc.p, tsc.p + (size_t)5 * B, MSM_MONT, 5 * B, Tc.p, B, 0, st, stats);
+        dev_zero(tsc.p, tsc.bytes(), st);   // (blindings)
+    } else
     launch_commit_T(K_commit_T{g->tab.p, g->tc, tco.p, blind.p, Tc.p, B}, B, st);
     K_transcript_T ktt{tr.p, Tc.p, tco.p, blind.p, wvec.p + (size_t)3 * n * B, vbl_m.p, chal.p, txs.p, B, m, (uint64_t)N};
     DevBuf<sc> t2b_pre;
@@ -602,6 +631,7 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     pt.mark(st);
 
     // ---- P5: inner-product argument
+    MSM_TRACE_F2_MUTE(1);   // (simulator's recorder: the commit phase ends here)
     IpaIO io{g, B, N, lgN, (uint32_t)o_unfold, tr.p, a.p, bb.p, cG.p, cH.p, chal.p + (size_t)CH_W * B, nullptr, LR.p, uk.p};
     // same box, alternating runs: 2957 / 2960 against 2948 / 2955 proofs/s for the depth-32 circuit (the term fetch costs a launch 3.3 ms, the
     // kernel it replaces took 26 ms per job); nothing for N = 512 / 1024 (148.7 against 149.1 k, 83.26 against 83.29 k): from N = 4096 on
@@ -739,7 +769,7 @@ static uint32_t auto_job_proofs(const bpr1cs_gens* g, const bpr1cs_circuit* c, b
     const size_t others = 32 * (3 * n + m + nfl) + 64 * N, vt = r < c->lgN ? (size_t)VB_MULT * 4 * std::max<size_t>(1, Mr / 2) * sizeof(ge_cached) : 0;
     const size_t back = std::max(others, vt) + 64 * N + 2 * VB_WINDOWS * sizeof(ge) + 30000;   // (folded generators, digits, window sums: inside the dead rows of l / r)
     size_t fixed = (size_t)5 << 29;   // chunk partial sums of the MSM launches (~2^21 points each, whatever the batch: six buffers in the shared arena), staging
-    if (have_program && !c->h_trip.empty()) {
+    if (have_program && !c->h_trip.empty() && !g->ct()) {   // (a secret-independent handle takes the plain sums: no merged tables)
         std::lock_guard<std::mutex> lk(c->mt_mu);
         auto it = c->mt.find(g);
         if (it == c->mt.end() || !it->second->tab.p) fixed += 2 * c->h_trip.size() * merged_tab_cfg(g, (uint32_t)c->h_trip.size()).base_bytes();

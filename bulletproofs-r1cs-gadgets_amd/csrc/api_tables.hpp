@@ -77,7 +77,8 @@ int bpr1cs_gens_create_opts(uint32_t cap, const int32_t* pairs, size_t n_pairs, 
         window_bits = 8;   // (the simulator builds its tables on one CPU core)
 #else
         window_bits = 4;
-        const double freeb = (double)dev_free_memory();
+        // (the narrow table set of BPR1CS_OPT_SECRET_INDEPENDENT is charged first: W is chosen from what is left)
+        const double freeb = std::max(0.0, (double)dev_free_memory() - (g->opts.secret_independent ? (double)(2 + 2 * (size_t)cap) * (double)tab_cfg(MSM_CT_W).base_bytes() : 0.0));
         auto bytes_at = [&](int w) { return (double)(2 + 2 * (size_t)cap) * (double)tab_cfg((uint32_t)w).base_bytes(); };
         int pick = 0;
         for (int w = 15; w >= 12 && !pick; w--)
@@ -117,6 +118,11 @@ int bpr1cs_gens_create_opts(uint32_t cap, const int32_t* pairs, size_t n_pairs, 
     g->comp.resize((size_t)nb * 32);
     dev_d2h(g->comp.data(), d_comp.p, (size_t)nb * 32, g->stream);
     memcpy(g->comp.data(), bcomp, 32);
+    if (g->opts.secret_independent) {   // before the wide set: an allocation failure here leaves nothing half-built behind it
+        g->tc_ct = tab_cfg(MSM_CT_W);
+        g->tab_ct.alloc((size_t)nb * g->tc_ct.base_bytes());
+        launch((uint64_t)nb * g->tc_ct.windows, K_build_table{g->pts.p, g->tab_ct.p, g->tc_ct}, g->stream);
+    }
     g->tab.alloc((size_t)nb * g->tc.base_bytes());
     launch((uint64_t)nb * g->tc.windows, K_build_table{g->pts.p, g->tab.p, g->tc}, g->stream);
     dev_sync(g->stream);

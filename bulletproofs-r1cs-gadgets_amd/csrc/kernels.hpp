@@ -946,6 +946,33 @@ struct K_commit_T {  // gid = k*B + b, k<5 : T = t*B + tau*B~  (t1,t3,t4,t5,t6)
     }
 };
 
+// BPR1CS_OPT_SECRET_INDEPENDENT: the V's and the T's are sums of k_msm_fixed_ct over the rows of B and B~ with one output per
+// "proof" of the launch; what is left for a kernel of their own is public work - the scalars of the five T's side by side, and the
+// sum of an output's chunk sums with its compression
+struct K_ct_gather_T {  // gid = k*B + b, k < 5: out[0][g] = t-coefficient, out[1][g] = its blinding (both Montgomery, as stored)
+    const sc* tco;    // [6][B]
+    const sc* blind;  // [8][B]
+    sc* out;          // [2][5B]
+    uint32_t B;
+    HD void operator()(uint32_t g) const {
+        const uint32_t k = g / B, b = g % B;
+        const uint32_t ti[5] = {0, 2, 3, 4, 5};
+        out[g] = tco[(size_t)ti[k] * B + b];
+        out[(size_t)5 * B + g] = blind[(size_t)(3 + k) * B + b];
+    }
+};
+struct K_ct_finish {  // gid = g (< count): compress(sum of the chunk sums of output g)
+    const ge* partial;  // [nchunks][count]
+    uint32_t nchunks, count;
+    uint8_t* out;       // m = 0: [count][32]; m > 0: output g = j*B + b goes to [b][j] of [B][m][32] (the V's)
+    uint32_t B, m;
+    HD void operator()(uint32_t g) const {
+        ge acc = partial[g];
+        for (uint32_t c = 1; c < nchunks; c++) acc = ge_add_ge(acc, partial[(size_t)c * count + g]);
+        ge_compress(acc, out + 32 * (m ? (size_t)(g % B) * m + g / B : (size_t)g));
+    }
+};
+
 // append T_*, u, x ; t_x, t_x_blinding, e_blinding ; w ; ipp dom-sep + n
 struct K_transcript_T {
     strobe* tr;

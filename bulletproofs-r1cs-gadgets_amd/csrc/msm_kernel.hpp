@@ -18,6 +18,7 @@
 //   * Signed digits without selects: a per-lane polarity of the accumulator (see the loop body).
 #pragma once
 #include "kernels.hpp"
+#include "msm_trace.hpp"   // (simulator-only recorder: MSM_TRACE expands to nothing in the device build)
 
 struct MsmJob {
     MsmSeg seg[2];
@@ -192,7 +193,9 @@ MSM_FN void msm_fixed2_body(const MsmLaunch& L, uint32_t wg_raw, const uint32_t 
             x = scalar_of(b);
             if (form == MSM_MINUS_ONE) t.mont = MSM_MONT;
             if (form >= MSM_GEO_G) t.mont = MSM_CANONICAL;
-            if (MsmWave::any(!sc_is_zero(x), [&](uint32_t l) { return !sc_is_zero(scalar_of(b0 + l < B ? b0 + l : B - 1)); })) return true;
+            const bool live = MsmWave::any(!sc_is_zero(x), [&](uint32_t l) { return !sc_is_zero(scalar_of(b0 + l < B ? b0 + l : B - 1)); });
+            MSM_TRACE_F2(MSM_TR_VOTE, live);
+            if (live) return true;
         }
         return false;
     };
@@ -207,6 +210,7 @@ MSM_FN void msm_fixed2_body(const MsmLaunch& L, uint32_t wg_raw, const uint32_t 
     uint32_t d = 0;
     if (have) {
         d = msm_dig[lane];
+        MSM_TRACE_F2(MSM_TR_TABLE, T.tab + (size_t)(d & 0x7fffu) * tc.stride - J.tab);
         msm_entry_load(E, T.tab + (size_t)(d & 0x7fffu) * tc.stride);
     }
     while (have) {
@@ -241,9 +245,11 @@ MSM_FN void msm_fixed2_body(const MsmLaunch& L, uint32_t wg_raw, const uint32_t 
             if (k + 1 < tc.windows) {
                 d = msm_dig[cur * dig_buf + (k + 1) * 64u + lane];
                 const uint8_t* rowp = T.tab + (size_t)(k + 1) * row_bytes;
+                MSM_TRACE_F2(MSM_TR_TABLE, rowp + (uint32_t)((d & 0x7fffu) * tc.stride) - J.tab);
                 msm_entry_load(E, rowp + (uint32_t)((d & 0x7fffu) * tc.stride));
             } else if (have2) {
                 d = msm_dig[(cur ^ 1u) * dig_buf + lane];
+                MSM_TRACE_F2(MSM_TR_TABLE, T2.tab + (uint32_t)((d & 0x7fffu) * tc.stride) - J.tab);
                 msm_entry_load(E, T2.tab + (uint32_t)((d & 0x7fffu) * tc.stride));
             }
             MSM_SCHED_FENCE();

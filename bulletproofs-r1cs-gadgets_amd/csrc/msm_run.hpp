@@ -196,6 +196,8 @@ static void launch_msm_kernel(const bpr1cs_gens* g, MsmLaunch& L, dev_stream_t s
     for (uint32_t r = 0; r < L.njobs; r++) L.max_windows = std::max(L.max_windows, L.job[r].tc.windows);
 #if defined(BPR1CS_HOSTSIM)
     (void)g; (void)st;
+    msm_trace().fixed2_launches++;
+    MSM_TRACE_F2(MSM_TR_GRID, L.nwg);
     msm_fixed2_sim(L);
     if (stats) { stats->launches++; stats->terms += terms; stats->adds += adds; }
 #else
@@ -216,6 +218,36 @@ static void launch_msm_kernel(const bpr1cs_gens* g, MsmLaunch& L, dev_stream_t s
     }
 #endif
 }
+// one launch of k_msm_fixed_ct (BPR1CS_OPT_SECRET_INDEPENDENT): same geometry, the narrow table set; counted in the same statistics
+static void launch_msm_ct_kernel(MsmLaunch& L, dev_stream_t st, MsmStats* stats, uint64_t terms, uint64_t adds) {
+    L.nwg = (L.wg_end[L.njobs - 1] + 7u) & ~7u;
+    L.max_windows = MSM_CT_WINDOWS;
+    for (uint32_t r = 0; r < L.njobs; r++)   // the kernel's digit buffer is sized for the narrow set, and it takes stored scalars only
+        if (L.job[r].tc.windows != MSM_CT_WINDOWS || L.job[r].interleave || L.job[r].seg[0].geo || L.job[r].seg[1].geo ||
+            L.job[r].seg[0].mont > MSM_MONT || L.job[r].seg[1].mont > MSM_MONT) throw DevError{BPR1CS_ERR_INVALID_ARGUMENT};
+#if defined(BPR1CS_HOSTSIM)
+    (void)st;
+    msm_trace().ct_launches++;
+    MSM_TRACE(MSM_TR_GRID, L.nwg);
+    msm_fixed_ct_sim(L);
+    if (stats) { stats->launches++; stats->terms += terms; stats->adds += adds; }
+#else
+    hipEvent_t e0{}, e1{};
+    if (stats) {
+        e0 = stats->get(); e1 = stats->get();
+        stats->ev.push_back({e0, e1});
+        HIPCHK(hipEventRecord(e0, st));
+    }
+    hipLaunchKernelGGL(k_msm_fixed_ct, dim3(L.nwg), dim3(64), 0, st, L);
+    HIPCHK(hipGetLastError());
+    if (stats) {
+        HIPCHK(hipEventRecord(e1, st));
+        stats->launches++;
+        stats->terms += terms;
+        stats->adds += adds;
+    }
+#endif
+}
 struct MsmReq {
     MsmSeg s0, s1;
     DevBuf<ge>* partial;  // out: the reduced partial sums sit at the front, [plan->nchunks][B]
@@ -225,8 +257,11 @@ struct MsmReq {
                               // proofs (MSM_MINUS_ONE) take few, long chunks: an empty workgroup still costs its dispatch
     const TabCfg* tc = nullptr;  // geometry of `table` (nullptr: that of the generator tables)
 };
-static void run_msm_multi(const bpr1cs_gens* g, MsmReq* reqs, uint32_t nreq, uint32_t B, dev_stream_t st, MsmStats* stats, const MsmGeo* geo = nullptr) {
-    if (B <= MSM_LANE_PATH_MAX_PROOFS) {  // a wavefront per (chunk, 64 proofs) would be mostly idle: lanes take different chunks instead
+// ct: the sums of a secret-independent handle's commit phase - k_msm_fixed_ct over the narrow table set whatever the batch (a job of
+// a few proofs fills few lanes of its wavefronts: a wavefront-per-output constant-time form does not exist), chunking from
+// the term count and B alone
+static void run_msm_multi(const bpr1cs_gens* g, MsmReq* reqs, uint32_t nreq, uint32_t B, dev_stream_t st, MsmStats* stats, const MsmGeo* geo = nullptr, bool ct = false) {
+    if (B <= MSM_LANE_PATH_MAX_PROOFS && !ct) {  // a wavefront per (chunk, 64 proofs) would be mostly idle: lanes take different chunks instead
         // the chunk sums are folded until at most MSM_REDUCE_GROUP are left for the per-proof finish kernel: 64 at a time inside the
         // wavefronts that computed them (k_msm_small_wave), then MSM_REDUCE_GROUP at a time (K_ge_reduce) - with ONE proof a 65 536-term
         // sum is 65 536 chunks (one term per lane) -> 1024 -> 64 -> 4
@@ -327,7 +362,8 @@ static void run_msm_multi(const bpr1cs_gens* g, MsmReq* reqs, uint32_t nreq, uin
     for (uint32_t r = 0; r < nreq; r++) {
         MsmReq& q = reqs[r];
         uint32_t total = q.s0.count + q.s1.count;
-        uint32_t nchunks = pick_chunks(total, B, 1u << g->opts.msm_threads_log2.load(), q.plan->chunk);
+        // (ct, few proofs: a wavefront carries B lanes of work, so the launch is sized in wavefronts - 64 lanes per chunk)
+        uint32_t nchunks = pick_chunks(total, ct ? nbk * 64u : B, 1u << g->opts.msm_threads_log2.load(), q.plan->chunk);
         if (q.chunk_hint) {
             q.plan->chunk = q.chunk_hint;
             nchunks = total ? (total + q.chunk_hint - 1) / q.chunk_hint : 1;
@@ -344,16 +380,28 @@ static void run_msm_multi(const bpr1cs_gens* g, MsmReq* reqs, uint32_t nreq, uin
         lay[r] = Lay{nchunks, l1, l2, q.partial->p + (size_t)(l1 + l2) * B, q.partial->p + (size_t)l2 * B, q.partial->p};
         q.plan->nchunks = l2 ? l2 : (l1 ? l1 : nchunks);
         terms += (uint64_t)total * B;
-        adds += (uint64_t)total * B * (q.tc ? q.tc->windows : g->tc.windows);
+        adds += (uint64_t)total * B * (ct ? g->tc_ct.windows : q.tc ? q.tc->windows : g->tc.windows);
         wg += nchunks * nbk;
-        L.job[r] = MsmJob{{q.s0, q.s1}, q.table ? q.table : g->tab.p, q.tc ? *q.tc : g->tc, lay[r].raw, q.plan->chunk, nchunks, 0};
+        if (ct) L.job[r] = MsmJob{{q.s0, q.s1}, g->tab_ct.p, g->tc_ct, lay[r].raw, q.plan->chunk, nchunks, 0};
+        else L.job[r] = MsmJob{{q.s0, q.s1}, q.table ? q.table : g->tab.p, q.tc ? *q.tc : g->tc, lay[r].raw, q.plan->chunk, nchunks, 0};
         L.wg_end[r] = wg;
     }
-    launch_msm_kernel(g, L, st, stats, terms, adds);
+    if (ct) launch_msm_ct_kernel(L, st, stats, terms, adds);
+    else launch_msm_kernel(g, L, st, stats, terms, adds);
     for (uint32_t r = 0; r < nreq; r++) {
         if (lay[r].l1) launch((uint64_t)lay[r].l1 * B, K_ge_reduce{lay[r].raw, lay[r].p1, B, lay[r].nchunks, MSM_REDUCE_GROUP}, st);
         if (lay[r].l2) launch((uint64_t)lay[r].l2 * B, K_ge_reduce{lay[r].p1, lay[r].p2, B, lay[r].l1, MSM_REDUCE_GROUP}, st);
     }
+}
+// secret-independent Pedersen commitments: out(g) = s0[g] * B + s1[g] * B~ for g < count (`form`: how both arrays are stored); m as K_ct_finish
+static void run_commit_ct(const bpr1cs_gens* g, const sc* s0, const sc* s1, uint32_t form, uint32_t count, uint8_t* out, uint32_t B, uint32_t m,
+                          dev_stream_t st, MsmStats* stats) {
+    if (!count) return;
+    DevBuf<ge> partial;
+    MsmPlan plan;
+    MsmReq q{MsmSeg{s0, 1, 1, 1, 0, 0, form}, MsmSeg{s1, 1, 1, 1, 0, 1, form}, &partial, &plan, nullptr};
+    run_msm_multi(g, &q, 1, count, st, stats, nullptr, true);
+    launch(count, K_ct_finish{partial.p, plan.nchunks, count, out, B, m}, st);
 }
 static void run_msm(const bpr1cs_gens* g, MsmSeg s0, MsmSeg s1, uint32_t B, DevBuf<ge>& partial, MsmPlan& plan, dev_stream_t st,
                     MsmStats* stats, const uint8_t* table = nullptr) {
@@ -370,3 +418,19 @@ static void run_flatten(const bpr1cs_circuit* c, uint32_t nslots, const sc* plo,
     launch((uint64_t)nch * B, K_flatten_chunks{c->chunk_lo.p, c->ent_row.p, c->ent_coeff.p, plo, phi, part_buf, B, H}, st);
     launch((uint64_t)nslots * B, K_flatten{c->slot_chunk.p, part_buf, wvec, B, 3 * c->n}, st);
 }
+
+#if defined(BPR1CS_HOSTSIM)
+// Simulator only (never part of libbpr1cs_hip.so): the recorder of msm_trace.hpp.  `out`, when given, receives what was recorded so
+// far - MSM_TR_KINDS counts, MSM_TR_KINDS hashes, then the launches of k_msm_fixed_ct's and of k_msm_fixed2's body since the last
+// reset.  mode 1: reset and switch on, 0: switch off, anything else: read only.
+extern "C" void bpr1cs_sim_msm_trace(int mode, uint64_t* out) {
+    MsmTrace& t = msm_trace();
+    if (out) {
+        for (uint32_t k = 0; k < MSM_TR_KINDS; k++) { out[k] = t.count[k]; out[MSM_TR_KINDS + k] = t.hash[k]; }
+        out[2 * MSM_TR_KINDS] = t.ct_launches;
+        out[2 * MSM_TR_KINDS + 1] = t.fixed2_launches;
+    }
+    if (mode == 1) { t = MsmTrace(); t.on = 1; }   // (also un-mutes msm_fixed2_body's hooks)
+    else if (mode == 0) t.on = 0;
+}
+#endif

@@ -23,10 +23,15 @@
  * library never aborts the process.  All scalar inputs must be canonical (< l);
  * non-canonical scalars are refused with BPR1CS_ERR_INVALID_ARGUMENT.
  *
- * TIMING SIDE CHANNELS - this library is NOT constant time, the reference's prover is.  Upstream computes A_I, A_O, S
- * (sums over the secret wires and blindings) with curve25519-dalek's constant-time `multiscalar_mul` and the L_k / R_k of
- * the inner-product argument with `vartime_multiscalar_mul` (public after the fact).  Here every multiscalar
- * multiplication runs through k_msm_fixed2, which (i) gathers table entries at addresses that are the signed digits of
+ * TIMING SIDE CHANNELS - by default this library is NOT constant time; a handle created with BPR1CS_OPT_SECRET_INDEPENDENT = 1
+ * gives the commit phase the property the reference's prover has for it.  Upstream computes the V's, A_I, A_O, S and the T's
+ * (sums over the secret values, wires and blindings) with curve25519-dalek's constant-time code and the L_k / R_k of
+ * the inner-product argument with `vartime_multiscalar_mul` (public after the fact).  With the option on, exactly those
+ * quantities are computed by k_msm_fixed_ct, which reads whole table rows at wave-uniform addresses and selects by scan: no
+ * address, branch, vote or grid of the commit phase depends on a secret.  Outside that contract in either mode, as upstream or
+ * public: the inner-product rounds, the verifier, the witness program (it branches on committed bits, as the reference's gadget
+ * code does on the host), the host front-end, compression of the resulting points.  Keccak / STROBE is data-independent.
+ * With the option off (the default) every multiscalar multiplication runs through k_msm_fixed2, which (i) gathers table entries at addresses that are the signed digits of
  * the secret scalars (memory-access pattern = secret), (ii) skips a term when the scalars of all 64 proofs of a
  * wavefront are zero, and (iii) takes the a_O wires of Inverse-S-box triples in the form a_O - 1, so that a proof whose
  * S-box input is 0 (an unsatisfiable witness: is_nonzero fails) makes its wavefront do work the others skip.  The witness
@@ -189,6 +194,15 @@ int bpr1cs_gens_table_info(const bpr1cs_gens* g, uint32_t* window_bits, uint32_t
                                          capacity 32768 on a 288 GB device, 8 / 7 for the reference's as-shipped tree depths (N = 131072 /
                                          262144, gadget_vsmt_4.rs:25, gadget_vsmt_2.rs:23).  A process that creates several handles, or
                                          wants small tables for a latency-only use, passes W explicitly (W = 8: 1/12 of the bytes) */
+#define BPR1CS_OPT_SECRET_INDEPENDENT 11 /* creation only: 0 (default) or 1, anything else BPR1CS_ERR_INVALID_ARGUMENT.  1 = the commit phase of
+                                         the prover - the V_j (in a prove job and in the pc_gens.commit shape of bpr1cs_msm_fixed: two terms
+                                         over B and B~; its general form stays variable time), A_I1, A_O1, S1 with their blinding terms, and
+                                         T_1, T_3, T_4, T_5, T_6 - runs through k_msm_fixed_ct: for a fixed (circuit, batch size, handle
+                                         options) its sequence of memory addresses, branch outcomes and launched grids does not depend on
+                                         committed values, wires, blindings or TranscriptRng draws (see TIMING SIDE CHANNELS above).  Same
+                                         bytes as with 0.  Costs a second, narrow table set for all 2 + 2*cap bases (4-bit windows: 64 x 9
+                                         slots x 128 B = 73.7 KB per base, 4.8 GB at capacity 32768), charged to the handle before W and the
+                                         job size are chosen, and 64 instead of 23 additions per term over plain n-term sums */
 int bpr1cs_gens_set_option(bpr1cs_gens* g, int option, int value);
 /* bpr1cs_gens_create with options: `pairs` = n_pairs x (option, value).  BPR1CS_ERR_INVALID_ARGUMENT for an unknown option. */
 int bpr1cs_gens_create_opts(uint32_t gens_capacity, const int32_t* pairs, size_t n_pairs, bpr1cs_gens** out);

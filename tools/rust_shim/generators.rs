@@ -35,6 +35,16 @@ fn create(capacity: usize) -> Arc<GensHandle> {
     Arc::new(GensHandle(h))
 }
 
+/// a handle whose commit phase is secret-independent (BPR1CS_OPT_SECRET_INDEPENDENT = 1, creation only: include/bpr1cs.h)
+fn create_secret_independent(capacity: usize) -> Arc<GensHandle> {
+    let mut h = std::ptr::null_mut();
+    const OPT_SECRET_INDEPENDENT: i32 = 11; // BPR1CS_OPT_SECRET_INDEPENDENT (the generated bindings carry functions, structs and enums, no #define)
+    let pairs = [OPT_SECRET_INDEPENDENT, 1];
+    let rc = unsafe { ffi::bpr1cs_gens_create_opts(capacity as u32, pairs.as_ptr(), 1, &mut h) };
+    assert_eq!(rc, ffi::BPR1CS_OK, "bpr1cs_gens_create_opts({}, secret_independent) failed with {}", capacity, rc);
+    Arc::new(GensHandle(h))
+}
+
 /// the two Pedersen bases; `commit` is the 2-term fixed-base sum the prover calls per committed value
 #[derive(Clone)]
 pub struct PedersenGens {
@@ -58,6 +68,17 @@ impl Default for PedersenGens {
 }
 
 impl PedersenGens {
+    /// as `default()`, on a handle of its own whose `commit` runs through the secret-independent kernel (upstream's `commit` is constant time)
+    pub fn secret_independent() -> Self {
+        let handle = create_secret_independent(1);
+        let mut b = [0u8; 32];
+        let mut bb = [0u8; 32];
+        unsafe {
+            ffi::bpr1cs_gens_point(handle.0, 0, 0, b.as_mut_ptr());
+            ffi::bpr1cs_gens_point(handle.0, 1, 0, bb.as_mut_ptr());
+        }
+        PedersenGens { B: CompressedRistretto(b), B_blinding: CompressedRistretto(bb), handle }
+    }
     /// `pc_gens.commit(v, blinding)` -> v * B + blinding * B_blinding
     pub fn commit(&self, value: Scalar, blinding: Scalar) -> CompressedRistretto {
         let bases = [0u32, 1u32];
@@ -83,6 +104,12 @@ impl BulletproofGens {
     pub fn new(gens_capacity: usize, party_capacity: usize) -> Self {
         assert_eq!(party_capacity, 1, "the R1CS gadgets of the reference are single-party");
         BulletproofGens { gens_capacity, party_capacity, handle: create(gens_capacity) }
+    }
+    /// the same generators on a handle created with BPR1CS_OPT_SECRET_INDEPENDENT = 1: A_I, A_O, S and the T's of every proof made with it
+    /// are computed by k_msm_fixed_ct (a second, narrow table set: 73.7 KB per generator)
+    pub fn new_secret_independent(gens_capacity: usize, party_capacity: usize) -> Self {
+        assert_eq!(party_capacity, 1, "the R1CS gadgets of the reference are single-party");
+        BulletproofGens { gens_capacity, party_capacity, handle: create_secret_independent(gens_capacity) }
     }
     /// G_i / H_i as upstream's `share(0).G(n)` / `.H(n)` iterators would yield them (compressed)
     pub fn point(&self, h_side: bool, i: usize) -> CompressedRistretto {
