@@ -14,6 +14,10 @@
 //     ge.hpp is one of N*N, 2N*2N, 2N*3N, 3N*3N, 3N*4N, 2N*4N (see the comments there);
 //     fe_sq accepts |limb| <= 2N.
 //   * values unpacked from canonical bytes have limbs in [0, 2^29) (class 2N).
+// Evidence for these bounds: the worst-case limb patterns of every class, single-limb operands that put 0x00000000, 0x7fffffff,
+// 0x80000000 and 0xffffffff into each pass-1 remainder word, and all limbs at the end of their class (the largest carry out of
+// column 8) - tests/prim_cases.py - go through the portable bodies below in tests/test_hostsim_prims.py and through the
+// device bodies (fe_asm_gfx950.inc) in tests/test_gpu_prims.py, each compared with big integers.
 //
 // Replaces (for the hot path) curve25519-dalek's FieldElement51 (reference Cargo.toml:8).
 #pragma once

@@ -10,7 +10,8 @@
 //   * limbs 9..18 come down nine lanes (DPP row_shl:9 for those of row 0, v_permlane16_swap + row_shr:7 for lanes 16..18) and
 //     enter as 1216 * l[k+9] (2^261 = 1216 mod p); a last round leaves 9 limbs.
 // Result limbs: lane 0 in (-2^13, 2^29 + 2^23), lanes 1..8 in (-2^13, 2^29 + 2^13); lanes >= 9 zero.  Inputs of that class (or
-// fe.hpp's class N) keep every column below 2^62.  Device only; the whole wavefront must call these functions together.
+// fe.hpp's class N) keep every column below 2^62 (tests/test_gpu_prims.py feeds fw_mul the ends of both classes and compares
+// with big integers).  Device only; the whole wavefront must call these functions together.
 #pragma once
 #include "fe.hpp"
 __device__ fe fe_pow22523_wave(const fe& z0);   // (the host pass of the compiler sees the declaration only)

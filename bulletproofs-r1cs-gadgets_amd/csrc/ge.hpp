@@ -142,7 +142,9 @@ HD inline ge ge_madd(const ge& p, const ge_niels& q, int negate) {
 //   X' = cX cT : 9 * 1.04F' * 3N = 2^61.8 ;  Y' = cY cZ : 9 * 2F' * 3N = 2^62.8 ;  T' = cX cY : 9 * 1.04F' * 2F' = 2^62.3  (fe_mul_f)
 //   Z' = cZ cT : 9 * 3N * 3N = 2^62.4                                                               (fe_mul, centred)
 // all below the 2^63 limit of the signed 64-bit column sums (tests/test_hostsim_prims.py drives the worst-case limb patterns of
-// every class through the multipliers and through the whole addition).  Six of the seven products use the floor-carry form;
+// every class through the multipliers and through the whole addition as g++ compiles them for the CPU simulator;
+// tests/test_gpu_prims.py drives the same patterns through the device bodies, the generated column chains of
+// fe_asm_gfx950.inc).  Six of the seven products use the floor-carry form;
 // exactly one of C and Z' has to stay centred (with both in floor form cZ reaches 2^30 and Y' 2^63.2).
 HD inline ge ge_madd_t(const ge& p, const ge_niels& q, int negate) {
     fe a = fe_select(q.yplusx, q.yminusx, negate);

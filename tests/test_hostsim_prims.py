@@ -7,6 +7,9 @@ from pyref.ed import P, L, BASEPOINT, from_uniform_bytes
 from pyref.merlin import Transcript
 from pyref.ed import sc_to_bytes
 
+import prim_cases as pc
+from prim_cases import N, FP, val
+
 
 def _call(f, *ins, n=32):
     o = ctypes.create_string_buffer(n)
@@ -14,14 +17,8 @@ def _call(f, *ins, n=32):
     return o.raw, r
 
 
-def _vals():
-    rnd = random.Random(7)
-    edge = [0, 1, 2, 19, 38, P - 1, P, P + 1, 2**255 - 1, 2**255, 2**256 - 1, 2**256 - 38, 2**256 - 39, L - 1, L, L + 1, 2**252]
-    return [x.to_bytes(32, "little") for x in edge] + [bytes(rnd.getrandbits(8) for _ in range(32)) for _ in range(120)]
-
-
 def test_field_and_scalar_arithmetic(prim_lib):
-    vals = _vals()
+    vals = pc.vals()
     for a in vals:
         ia = int.from_bytes(a, "little")
         for b in vals[:20]:
@@ -38,30 +35,33 @@ def test_field_and_scalar_arithmetic(prim_lib):
 
 
 def test_variable_time_inverse_on_many_values(prim_lib):
-    rnd = random.Random(77)
-    vals = [1 << k for k in range(0, 253, 7)] + [L - (1 << k) for k in range(0, 250, 11)] + [(1 << k) - 1 for k in range(1, 253, 9)]
-    vals += [rnd.getrandbits(rnd.choice((8, 31, 60, 61, 120, 200, 252))) for _ in range(1500)]
-    for x in vals:
-        x %= L
+    for x in pc.inv_var_values():
         got = int.from_bytes(_call(prim_lib.hs_sc_inv_var, x.to_bytes(32, "little"))[0], "little")
         assert got == (pow(x, L - 2, L) if x else 0), hex(x)
 
 
 def test_group_and_encoding(prim_lib):
-    rnd = random.Random(9)
-    for _ in range(12):
-        w = bytes(rnd.getrandbits(8) for _ in range(64))
-        assert int.from_bytes(_call(prim_lib.hs_sc_wide, w)[0], "little") == int.from_bytes(w, "little") % L
-        assert _call(prim_lib.hs_uniform, w)[0] == from_uniform_bytes(w).compress()
-        k = bytes(rnd.getrandbits(8) for _ in range(32))
-        p = BASEPOINT * int.from_bytes(k, "little")
-        assert _call(prim_lib.hs_basemul, k)[0] == p.compress()
-        out, ok = _call(prim_lib.hs_decompress_recompress, p.compress())
-        assert ok and out == p.compress()
-        q = from_uniform_bytes(bytes(rnd.getrandbits(8) for _ in range(64)))
-        o4, ok = _call(prim_lib.hs_addsub, p.compress(), q.compress(), n=128)
-        assert ok and o4 == (p + q).compress() + (p - q).compress() + (p + q).compress() + (p - q).compress()
+    for c in pc.group_cases():
+        assert int.from_bytes(_call(prim_lib.hs_sc_wide, c["wide"])[0], "little") == c["wide_mod_l"]
+        assert _call(prim_lib.hs_uniform, c["wide"])[0] == c["uniform"]
+        assert _call(prim_lib.hs_basemul, c["k"])[0] == c["p"]
+        out, ok = _call(prim_lib.hs_decompress_recompress, c["p"])
+        assert ok and out == c["p"]
+        o4, ok = _call(prim_lib.hs_addsub, c["p"], c["q"], n=128)
+        assert ok and o4 == c["addsub"]
     assert _call(prim_lib.hs_decompress_recompress, b"\x01" + bytes(31))[1] == 0
+
+
+def test_encodings_accepted_and_rejected_as_the_oracle_does(prim_lib):
+    """ge_decompress on the directed encodings of prim_cases.encoding_cases (canonicity, sign of s, non-squares, t < 0,
+    y = 0): the flag is the oracle's verdict, and an accepted string recompresses to itself."""
+    cases = pc.encoding_cases()
+    assert sum(ok for _, ok in cases) >= 81 and sum(not ok for _, ok in cases) >= 100
+    for e, want in cases:
+        out, ok = _call(prim_lib.hs_decompress_recompress, e)
+        assert bool(ok) == want, e.hex()
+        if want:
+            assert out == e, e.hex()
 
 
 def test_merlin_transcript_and_rng(prim_lib):
@@ -83,116 +83,93 @@ def test_merlin_transcript_and_rng(prim_lib):
     assert ch.raw == sc_to_bytes(t.challenge_scalar(b"y"))
 
 
+I9, I27, I36 = ctypes.c_int32 * 9, ctypes.c_int32 * 27, ctypes.c_int32 * 36
+
+
+def _mul_exact_within(f, a, b, lo, hi):
+    out, ol = (ctypes.c_uint8 * 32)(), I9()
+    f(I9(*a), I9(*b), out, ol)
+    assert int.from_bytes(bytes(out), "little") == val(a) * val(b) % P, (a, b)
+    assert min(ol) >= lo and max(ol) <= hi, (a, b, list(ol))
+
+
+def _sq_exact_within_n(prim_lib, a):
+    out, ol = (ctypes.c_uint8 * 32)(), I9()
+    prim_lib.hs_fe_sq_limbs(I9(*a), out, ol)
+    assert int.from_bytes(bytes(out), "little") == val(a) ** 2 % P, a
+    assert max(abs(x) for x in ol) <= N, (a, list(ol))
+
+
 def test_field_limb_bounds(prim_lib):
     """9x29 signed-limb field (csrc/fe.hpp): worst-case limb classes of every product shape used in ge.hpp
     (N*N, 2N*2N, 2N*3N, 3N*3N, 3N*4N, 2N*4N; squares up to 2N) stay exact and return limbs within N."""
-    import ctypes, random
-    P = 2**255 - 19
-    N = 2**28 + 2**23
-    I9 = ctypes.c_int32 * 9
-    rnd = random.Random(29)
-
-    def val(l):
-        return sum(int(x) << (29 * i) for i, x in enumerate(l)) % P
-
-    def patterns(bound):
-        yield [bound] * 9
-        yield [-bound] * 9
-        yield [bound if i % 2 else -bound for i in range(9)]
-        yield [-bound if i % 2 else bound for i in range(9)]
-        for _ in range(40):
-            yield [rnd.choice((bound, -bound, rnd.randint(-bound, bound))) for _ in range(9)]
-
-    out = (ctypes.c_uint8 * 32)()
-    ol = I9()
-    for ka, kb in ((1, 1), (2, 2), (2, 3), (3, 3), (3, 4), (2, 4), (4, 1)):
-        for a in patterns(ka * N):
-            for b in list(patterns(kb * N))[:12]:
-                prim_lib.hs_fe_mul_limbs(I9(*a), I9(*b), out, ol)
-                assert int.from_bytes(bytes(out), "little") == val(a) * val(b) % P
-                assert max(abs(x) for x in ol) <= N
-    for a in patterns(2 * N):
-        prim_lib.hs_fe_sq_limbs(I9(*a), out, ol)
-        assert int.from_bytes(bytes(out), "little") == val(a) ** 2 % P
-        assert max(abs(x) for x in ol) <= N
-    for k in (1, 2, 3, 4, 7):
-        for a in patterns(k * N):
-            prim_lib.hs_fe_canon_limbs(I9(*a), out)
-            assert int.from_bytes(bytes(out), "little") == val(a)
-            prim_lib.hs_fe_carry_limbs(I9(*a), ol)
-            assert val(list(ol)) == val(a) and max(abs(x) for x in ol) <= N
+    mul, sq, carry = pc.field_limb_cases()
+    assert len(mul) == 7 * 44 * 12 and len(sq) == 44 and len(carry) == 5 * 44
+    out, ol = (ctypes.c_uint8 * 32)(), I9()
+    for a, b in mul:
+        _mul_exact_within(prim_lib.hs_fe_mul_limbs, a, b, -N, N)
+    for a in sq:
+        _sq_exact_within_n(prim_lib, a)
+    for a in carry:
+        prim_lib.hs_fe_canon_limbs(I9(*a), out)
+        assert int.from_bytes(bytes(out), "little") == val(a)
+        prim_lib.hs_fe_carry_limbs(I9(*a), ol)
+        assert val(list(ol)) == val(a) and max(abs(x) for x in ol) <= N
     # canonical edge values
-    for v in (0, 1, 19, P - 1, P, P + 1, 2**255 - 1, 2**255, 2**256 - 1):
-        limbs = [(v >> (29 * i)) & (2**29 - 1) for i in range(9)]
-        prim_lib.hs_fe_canon_limbs(I9(*limbs), out)
+    for v in pc.CANON_EDGE:
+        prim_lib.hs_fe_canon_limbs(I9(*pc.limbs_of(v)), out)
         assert int.from_bytes(bytes(out), "little") == v % P
+
+
+def test_remainder_word_extremes(prim_lib):
+    """Single-limb operands whose one non-zero column sum ends in 0x00000000, 0x7fffffff, 0x80000000 or 0xffffffff, for both
+    signs of the sum: the word pass 1 hands to the unsigned multiply-add of pass 2 (and column 8's own remainder)."""
+    cases = pc.remainder_word_mul_cases()
+    assert len(cases) == 45 * 4 * 2
+    for a, b, k, w, sign in cases:
+        _mul_exact_within(prim_lib.hs_fe_mul_limbs, a, b, -N, N)
+        _mul_exact_within(prim_lib.hs_fe_mul_f_limbs, a, b, -2**24, FP - 1)
+    sq = pc.remainder_word_sq_cases()
+    assert {(k, w) for _, k, w, _ in sq} >= {(k, w) for k in range(8, 16) for w in pc.REMAINDER_WORDS if not (k % 2 and w % 2)}
+    for a, k, w, sign in sq:
+        _sq_exact_within_n(prim_lib, a)
+
+
+def test_column8_carry_wrap(prim_lib):
+    """All nine limbs at the end of their class (and the one-limb-off neighbours): the largest column sums and the largest
+    carry out of column 8 into limb 0, for every class pair of test_field_limb_bounds and ge_madd_t's floor-carry classes."""
+    mul, mul_f, sq = pc.column8_wrap_cases()
+    assert len(mul) == 7 * 4 * 19 and len(mul_f) == 4 * 19 and len(sq) == 20
+    for a, b in mul:
+        _mul_exact_within(prim_lib.hs_fe_mul_limbs, a, b, -N, N)
+    for a, b in mul_f:
+        _mul_exact_within(prim_lib.hs_fe_mul_f_limbs, a, b, -2**24, FP - 1)
+    for a in sq:
+        _sq_exact_within_n(prim_lib, a)
 
 
 def test_table_class_limb_bounds(prim_lib):
     """ge_madd_t (csrc/ge.hpp): the table-addition chain keeps X, Y, T as floor-carry products (limbs in [-2^24, F'),
     F' = 2^29 + 2^24) and Z centred; worst-case limb patterns of that class must multiply exactly and return
     limbs of the same class, for both signs of the digit."""
-    import ctypes, random
-    P = 2**255 - 19
-    N = 2**28 + 2**23
-    FP = 2**29 + 2**24
-    I9, I27, I36 = ctypes.c_int32 * 9, ctypes.c_int32 * 27, ctypes.c_int32 * 36
-    rnd = random.Random(31)
-
-    def val(l):
-        return sum(int(x) << (29 * i) for i, x in enumerate(l)) % P
-
-    def floor_pat():
-        yield [FP - 1] * 9
-        yield [-2**24] * 9
-        yield [FP - 1 if i % 2 else -2**24 for i in range(9)]
-        for _ in range(6):
-            yield [rnd.choice((FP - 1, -2**24, 0, rnd.randint(0, 2**29 - 1))) for _ in range(9)]
-
-    def cent_pat():
-        yield [N] * 9
-        yield [-N] * 9
-        yield [N if i % 2 else -N for i in range(9)]
-        for _ in range(4):
-            yield [rnd.choice((N, -N, rnd.randint(-N, N))) for _ in range(9)]
-
-    def tab_pat():
-        yield [2**29 - 1] * 9
-        yield [0] * 9
-        for _ in range(3):
-            yield [rnd.choice((2**29 - 1, 0, rnd.randint(0, 2**29 - 1))) for _ in range(9)]
-
+    mul_f, madd = pc.table_class_cases()
+    assert len(mul_f) == 81 and len(madd) == 9 * 4 * 4 * 3 * 5 * 2
     out, ol = (ctypes.c_uint8 * 32)(), I9()
     # the floor-carry multiplier alone, on the largest operand classes ge_madd_t feeds it
-    for a in floor_pat():
-        for b in floor_pat():
-            a2 = [2 * x for x in a]                      # cY <= 2F'
-            b3 = [min(3 * N, max(-3 * N, 3 * x)) for x in b]  # |cZ|, |cT| <= N + F' = 3N in ge_madd_t (T*dxy in floor-carry form)
-            prim_lib.hs_fe_mul_f_limbs(I9(*a2), I9(*b3), out, ol)
-            assert int.from_bytes(bytes(out), "little") == val(a2) * val(b3) % P
-            assert min(ol) >= -2**24 and max(ol) < FP
+    for a2, b3 in mul_f:
+        prim_lib.hs_fe_mul_f_limbs(I9(*a2), I9(*b3), out, ol)
+        assert int.from_bytes(bytes(out), "little") == val(a2) * val(b3) % P
+        assert min(ol) >= -2**24 and max(ol) < FP
     o36, ob = I36(), (ctypes.c_uint8 * 128)()
-    for X in floor_pat():
-        for Y in list(floor_pat())[:4]:
-            for Z in list(cent_pat())[:4]:
-                for T in list(floor_pat())[:3]:
-                    for q in tab_pat():
-                        qq = list(q) + list(reversed(q)) + [q[(i * 5) % 9] for i in range(9)]
-                        for neg in (0, 1):
-                            prim_lib.hs_ge_madd_t_limbs(I36(*(X + Y + Z + T)), I27(*qq), neg, o36, ob)
-                            x, y, z, t = val(X), val(Y), val(Z), val(T)
-                            ypx, ymx, xy2d = val(qq[:9]), val(qq[9:18]), val(qq[18:])
-                            if neg:
-                                ypx, ymx, xy2d = ymx, ypx, -xy2d
-                            A, B, C, D = (y + x) * ypx, (y - x) * ymx, t * xy2d, z   # halved table form: Z, not 2Z
-                            cX, cY, cZ, cT = A - B, A + B, D + C, D - C
-                            want = [cX * cT % P, cY * cZ % P, cZ * cT % P, cX * cY % P]
-                            got = [int.from_bytes(bytes(ob)[32 * k:32 * k + 32], "little") for k in range(4)]
-                            assert got == want
-                            lim = list(o36)
-                            for k in (0, 1, 3):
-                                assert min(lim[9 * k:9 * k + 9]) >= -2**24 and max(lim[9 * k:9 * k + 9]) < FP
-                            assert max(abs(v) for v in lim[18:27]) <= N
+    for X, Y, Z, T, qq, neg in madd:
+        prim_lib.hs_ge_madd_t_limbs(I36(*(X + Y + Z + T)), I27(*qq), neg, o36, ob)
+        want = pc.madd_t_expect(X, Y, Z, T, qq, neg)
+        got = [int.from_bytes(bytes(ob)[32 * k:32 * k + 32], "little") for k in range(4)]
+        assert got == want
+        lim = list(o36)
+        for k in (0, 1, 3):
+            assert min(lim[9 * k:9 * k + 9]) >= -2**24 and max(lim[9 * k:9 * k + 9]) < FP
+        assert max(abs(v) for v in lim[18:27]) <= N
 
 
 def test_table_msm_formats_and_windows(prim_lib):
