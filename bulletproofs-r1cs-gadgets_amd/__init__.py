@@ -62,10 +62,12 @@ OPT_UNFOLD_ROUNDS, OPT_WITNESS_TEAM, OPT_TAIL_ROUNDS, OPT_SHARED_BACK, OPT_FACTO
 OPT_MSM_THREADS_LOG2, OPT_JOB_PROOFS, OPT_JOBS_IN_FLIGHT, OPT_HOST_CHAIN_PROOFS, OPT_WINDOW_BITS = 6, 7, 8, 9, 16
 OPT_HOST_CHAIN_SHARE = 10
 OPT_SECRET_INDEPENDENT = 11   # creation only: the commit phase through k_msm_fixed_ct
+OPT_VERIFY_GROUP, OPT_VERIFY_GROUP_FALLBACK = 12, 13   # verify_batch: one combined check per group of proofs, re-check of a failing group
 OPTIONS = dict(unfold=OPT_UNFOLD_ROUNDS, witness_team=OPT_WITNESS_TEAM, tail_rounds=OPT_TAIL_ROUNDS, shared_back=OPT_SHARED_BACK,
                factor_vectors=OPT_FACTOR_VECTORS, msm_threads_log2=OPT_MSM_THREADS_LOG2, job_proofs=OPT_JOB_PROOFS,
                jobs_in_flight=OPT_JOBS_IN_FLIGHT, host_chain_proofs=OPT_HOST_CHAIN_PROOFS, window_bits=OPT_WINDOW_BITS,
-               host_chain_share=OPT_HOST_CHAIN_SHARE, secret_independent=OPT_SECRET_INDEPENDENT)
+               host_chain_share=OPT_HOST_CHAIN_SHARE, secret_independent=OPT_SECRET_INDEPENDENT,
+               verify_group=OPT_VERIFY_GROUP, verify_group_fallback=OPT_VERIFY_GROUP_FALLBACK)
 
 
 class ProveStats(ctypes.Structure):

@@ -144,8 +144,9 @@ struct CombinedCtx {
     const ge* own = nullptr;
     uint32_t own_cnt = 0;
 };
-static void verify_combine(CombinedCtx& k, VerifyCtx& v, const uint8_t* batch_seed, uint64_t index_base, dev_stream_t st) {
-    const uint32_t B = v.B, N = v.N;
+// the weights rho_b (Montgomery) of a batch whose transcripts were replayed with binding values (verify_front, want_bind)
+static void verify_weights(CombinedCtx& k, VerifyCtx& v, const uint8_t* batch_seed, uint64_t index_base, dev_stream_t st) {
+    const uint32_t B = v.B;
     k.d_bseed.alloc(32); k.digest.alloc(32); k.rho.alloc(B);
     dev_h2d(k.d_bseed.p, batch_seed, 32, st);
     const uint32_t leaves = (B + BATCH_LEAF - 1) / BATCH_LEAF;
@@ -153,6 +154,10 @@ static void verify_combine(CombinedCtx& k, VerifyCtx& v, const uint8_t* batch_se
     launch(leaves, K_batch_leaf{v.bind.p, leaf.p, B}, st);
     launch(1, K_batch_digest{k.d_bseed.p, leaf.p, k.digest.p, index_base, B}, st);
     launch(B, K_batch_weights{k.digest.p, k.rho.p, index_base}, st);
+}
+static void verify_combine(CombinedCtx& k, VerifyCtx& v, const uint8_t* batch_seed, uint64_t index_base, dev_stream_t st) {
+    const uint32_t B = v.B, N = v.N;
+    verify_weights(k, v, batch_seed, index_base, st);
     k.cgh.alloc((size_t)2 * N); k.cb.alloc(2);
     launch((uint64_t)2 * N, K_combine_scalars{v.gh.p, k.rho.p, k.cgh.p, B}, st);
     launch(2, K_combine_scalars{v.bsc.p, k.rho.p, k.cb.p, B}, st);
@@ -214,6 +219,127 @@ static int verify_batch_combined_once(const bpr1cs_gens* g, const bpr1cs_circuit
     dev_d2h(partial_point_out, d_out.p, 32, st);
     dev_d2h(wellformed_out, d_wf.p, sizeof(int), st);
     stats.collect();
+    return BPR1CS_OK;
+    API_CATCH
+}
+
+// Grouped verification (BPR1CS_OPT_VERIFY_GROUP): the batch in NG = ceil(B / G) groups of G consecutive proofs, one combined
+// identity test per group - the shared-base sum is one fixed-base MSM of batch NG over the segmented combination cgh[2N][NG] of the
+// proofs' scalar vectors - and the per-proof path only for the proofs of a group that fails (verify_batch_grouped_once).
+// Workgroups (one wavefront each) of k_combine_scalars_group_wave for rows x NG outputs.  A launch must stay below 2^32 threads in
+// all, and the depth-32 circuit (2N = 65536 rows) passes 2^26 outputs at NG = 1024 - 4096 proofs in groups of 4: the grid is capped and
+// a wavefront walks outputs a grid apart (2^20 wavefronts are 128 times what the chip holds at once; a 4096-proof job with G = 64 is
+// four outputs per wavefront).  The output index itself must fit 32 bits (verify_args_ok bounds 4N x batch, and NG <= (batch + 1) / 2).
+static const uint32_t GROUP_COMBINE_MAX_WGS = 1u << 20;
+static uint32_t combine_grouped_wgs(uint64_t rows, uint64_t NG) {
+    const uint64_t outputs = rows * NG;
+    if (rows > 0xffffffffull || NG > 0xffffffffull || outputs > 0xffffffffull) throw DevError{BPR1CS_ERR_INVALID_ARGUMENT};
+    return (uint32_t)std::min<uint64_t>(outputs, GROUP_COMBINE_MAX_WGS);
+}
+static void launch_combine_grouped(uint32_t rows, const K_combine_scalars_grouped& f, dev_stream_t st) {
+    const uint32_t wgs = combine_grouped_wgs(rows, f.NG);
+    if (!wgs) return;
+#if !defined(BPR1CS_HOSTSIM)
+    hipLaunchKernelGGL(k_combine_scalars_group_wave, dim3(wgs), dim3(64), 0, st, f, rows * f.NG);
+    HIPCHK(hipGetLastError());
+#else
+    launch((uint64_t)rows * f.NG, f, st);
+#endif
+}
+#if defined(BPR1CS_HOSTSIM)
+// Simulator only (never part of libbpr1cs_hip.so): the launch geometry above for a shape no test can afford to run - *wgs = workgroups
+// of 64 threads for rows x NG outputs; returns BPR1CS_ERR_INVALID_ARGUMENT where the output index does not fit 32 bits.
+extern "C" int bpr1cs_sim_group_combine_grid(uint64_t rows, uint64_t NG, uint32_t* wgs) {
+    if (!wgs) return BPR1CS_ERR_INVALID_ARGUMENT;
+    API_TRY
+    *wgs = combine_grouped_wgs(rows, NG);
+    return BPR1CS_OK;
+    API_CATCH
+}
+#endif
+// the device part: -> gok[NG] (the group's identity test held and none of its proofs is malformed), pfail[B] (proof is malformed)
+static int verify_groups_device(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len, const uint8_t* proofs,
+                                const uint8_t* commitments, const uint8_t* verifier_rng_seeds, size_t batch, uint32_t G,
+                                std::vector<int>& gok, std::vector<int>& pfail) {
+    API_TRY
+    dev_stream_t st = g->stream;
+    CallScope scope(st);
+    MsmStats stats;
+    VerifyCtx v;
+    verify_front(v, g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, true, st);
+    const uint32_t B = v.B, N = v.N, NG = (B + G - 1) / G, baseG = 2, baseH = 2 + g->cap;
+    // the entry point has no batch seed of its own: the first proof's verifier seed (zeros with none), bound to the whole batch by the digest
+    uint8_t bseed[32] = {0};
+    if (verifier_rng_seeds) memcpy(bseed, verifier_rng_seeds, 32);
+    CombinedCtx k;
+    verify_weights(k, v, bseed, 0, st);
+    k.cgh.alloc((size_t)2 * N * NG); k.cb.alloc((size_t)2 * NG);
+    launch_combine_grouped(2 * N, K_combine_scalars_grouped{v.gh.p, k.rho.p, k.cgh.p, B, G, NG}, st);
+    launch_combine_grouped(2, K_combine_scalars_grouped{v.bsc.p, k.rho.p, k.cb.p, B, G, NG}, st);
+    k.pts.alloc((size_t)v.P * B);
+    K_verify_points kp{v.d_pf.p, v.d_vc.p, v.chal.p, v.uk.p, v.wvec.p + (size_t)3 * v.n * B, k.pts.p, v.fail.p, B, v.m, v.lgN, (uint32_t)v.plen};
+    kp.rho = k.rho.p;
+    launch((uint64_t)v.P * B, kp, st);
+    DevBuf<ge> gpts(NG);
+    DevBuf<int> gfail(NG), ok(NG);
+    {
+        K_group_points kg{k.pts.p, v.fail.p, gpts.p, gfail.p, B, v.P, G};
+#if !defined(BPR1CS_HOSTSIM)
+        hipLaunchKernelGGL(k_group_points_wave, dim3(NG), dim3(64), 0, st, kg);
+        HIPCHK(hipGetLastError());
+#else
+        launch(NG, kg, st);
+#endif
+    }
+    DevBuf<ge> partial;
+    MsmPlan plan;
+    MsmSeg sg{k.cgh.p, N, N, N, 0, baseG, 0}, sh{k.cgh.p + (size_t)N * NG, N, N, N, 0, baseH, 0};
+    run_msm(g, sg, sh, NG, partial, plan, st, &stats);
+    {
+        K_verify_finish kf{g->tab.p, g->tc, partial.p, gpts.p, k.cb.p, gfail.p, ok.p, NG, plan.nchunks, 1};
+#if !defined(BPR1CS_HOSTSIM)
+        if (NG <= FINISH_WAVE_MAX_PROOFS) {
+            hipLaunchKernelGGL(k_verify_finish_wave, dim3(NG), dim3(64), 0, st, kf);
+            HIPCHK(hipGetLastError());
+        } else
+#endif
+        launch(NG, kf, st);
+    }
+    gok.resize(NG); pfail.resize(B);
+    dev_d2h(gok.data(), ok.p, sizeof(int) * NG, st);
+    dev_d2h(pfail.data(), v.fail.p, sizeof(int) * B, st);
+    stats.collect();
+    return BPR1CS_OK;
+    API_CATCH
+}
+static int verify_batch_grouped_once(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,
+                                     const uint8_t* proofs, const uint8_t* commitments, const uint8_t* verifier_rng_seeds, size_t batch,
+                                     uint32_t G, bool fallback, int* ok_out) {
+    if (!ok_out) return BPR1CS_ERR_INVALID_ARGUMENT;
+    int rc = verify_args_ok(g, c, label, proofs, commitments, batch);
+    if (rc) return rc;
+    std::vector<int> gok, pfail;
+    rc = verify_groups_device(g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, G, gok, pfail);
+    if (rc) return rc;
+    API_TRY
+    std::vector<size_t> redo;   // well-formed proofs of the groups that failed
+    for (size_t b = 0; b < batch; b++) {
+        ok_out[b] = gok[b / G];
+        if (!gok[b / G] && !pfail[b] && fallback) redo.push_back(b);
+    }
+    if (redo.empty()) return BPR1CS_OK;
+    // the inputs are host memory: the sub-batch is gathered here and takes the per-proof path as a batch of its own
+    const size_t plen = bpr1cs_proof_len(c), clen = (size_t)c->m * 32;
+    std::vector<uint8_t> sp(redo.size() * plen), sc_(redo.size() * clen + 1), ss(verifier_rng_seeds ? redo.size() * 32 : 0);
+    std::vector<int> sok(redo.size(), 0);
+    for (size_t i = 0; i < redo.size(); i++) {
+        memcpy(sp.data() + i * plen, proofs + redo[i] * plen, plen);
+        if (clen) memcpy(sc_.data() + i * clen, commitments + redo[i] * clen, clen);
+        if (verifier_rng_seeds) memcpy(ss.data() + i * 32, verifier_rng_seeds + redo[i] * 32, 32);
+    }
+    rc = verify_batch_once(g, c, label, label_len, sp.data(), sc_.data(), verifier_rng_seeds ? ss.data() : nullptr, redo.size(), sok.data());
+    if (rc) return rc;
+    for (size_t i = 0; i < redo.size(); i++) ok_out[redo[i]] = sok[i];
     return BPR1CS_OK;
     API_CATCH
 }
@@ -284,6 +410,11 @@ static int with_scratch_retry(const bpr1cs_gens* g, F&& once) {
 extern "C" int bpr1cs_verify_batch(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,
                                    const uint8_t* proofs, const uint8_t* commitments, const uint8_t* verifier_rng_seeds, size_t batch,
                                    int* ok_out) {
+    const int G = g ? g->opts.verify_group.load() : 0;
+    if (G >= 2 && batch >= 2) {
+        const bool fallback = g->opts.verify_group_fallback.load() != 0;
+        return with_scratch_retry(g, [&] { return verify_batch_grouped_once(g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, (uint32_t)G, fallback, ok_out); });
+    }
     return with_scratch_retry(g, [&] { return verify_batch_once(g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, ok_out); });
 }
 extern "C" int bpr1cs_verify_batch_combined(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,

@@ -19,6 +19,7 @@
 #include "sc.hpp"
 #include "ge.hpp"
 #include "merlin.hpp"
+#include "msm_trace.hpp"   // (simulator-only recorder: MSM_TRACE expands to nothing in the device build)
 
 // table geometry: W-bit signed windows -> windows = ceil(253/W), entries = 2^(W-1) per window.  A window row holds
 // entries + 1 slots: slot 0 is the identity (digit 0: the pipelined MSM kernel never branches on a digit), slot j
@@ -771,6 +772,7 @@ struct K_msm_fixed_small {  // gid = c*B + b -> partial[c*B + b]
             uint32_t oo = o < seg[0].count ? o : o - seg[0].count;
             uint32_t i = s.sidx ? s.sidx[oo] : (oo / s.run) * s.period + s.off + (oo % s.run);
             uint32_t base = s.base0 + (s.bdense ? oo : i);
+            MSM_TRACE_F2(MSM_TR_SCALAR, (size_t)i * B + b);
             sc x = s.scal[(size_t)i * B + b];
             x = msm_scalar(x, s.mont);
             acc = table_mul_acc_raw(acc, tab + (size_t)base * tc.base_bytes(), x, tc);
@@ -1821,6 +1823,41 @@ struct K_combine_scalars {  // gid = row : out[row] = sum_b in[row*B + b] * rho[
         const sc* r = in + (size_t)row * B;
         for (uint32_t b = 0; b < B; b++) acc = sc_add(acc, sc_mul(r[b], rho[b]));
         out[row] = acc;
+    }
+};
+// Grouped verification (BPR1CS_OPT_VERIFY_GROUP): the batch in groups of G consecutive proofs (the last may be short), one combined check per
+// group.  These functors are the definition of the two segmented sums; on the device a wavefront computes each output
+// (kernels_hip.hpp k_combine_scalars_group_wave, k_group_points_wave) - sums mod l and sums of points do not depend on the order.
+struct K_combine_scalars_grouped {  // gid = row*NG + grp : out[gid] = sum_{b in group grp} in[row*B + b] * rho[b]   (forms as K_combine_scalars)
+    const sc* in;
+    const sc* rho;  // Montgomery
+    sc* out;        // [rows][NG]
+    uint32_t B, G, NG;
+    HD void operator()(uint32_t g) const {
+        const uint32_t row = g / NG, grp = g % NG;
+        const uint32_t lo = grp * G, hi = lo + G < B ? lo + G : B;
+        sc acc = sc_zero();
+        const sc* r = in + (size_t)row * B;
+        for (uint32_t b = lo; b < hi; b++) acc = sc_add(acc, sc_mul(r[b], rho[b]));
+        out[g] = acc;
+    }
+};
+struct K_group_points {  // gid = grp : out[grp] = sum of the P weighted points of every proof of the group, gfail[grp] = OR of its proofs' flags
+    const ge* pts;    // [P][B]
+    const int* fail;  // [B]
+    ge* out;          // [NG]
+    int* gfail;       // [NG]
+    uint32_t B, P, G;
+    HD void operator()(uint32_t grp) const {
+        const uint32_t lo = grp * G, hi = lo + G < B ? lo + G : B;
+        ge acc = ge_identity();
+        int bad = 0;
+        for (uint32_t b = lo; b < hi; b++) {
+            for (uint32_t p = 0; p < P; p++) acc = ge_add_ge(acc, pts[(size_t)p * B + b]);
+            bad |= fail[b] != 0;
+        }
+        out[grp] = acc;
+        gfail[grp] = bad;
     }
 };
 struct K_batch_finish {  // single thread: sum of the partial sums -> compressed point, AND of the format checks

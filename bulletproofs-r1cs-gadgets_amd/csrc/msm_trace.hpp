@@ -2,8 +2,10 @@
 // address they form (relative to its buffer), every wave vote, every loop trip count and every launched grid goes through
 // MSM_TRACE(kind, value) into one running (count, hash) pair per kind.  tests/test_secret_independent.py proves a circuit twice with
 // different secrets and compares the recordings: equal for k_msm_fixed_ct's body (the contract of BPR1CS_OPT_SECRET_INDEPENDENT), different for
-// msm_fixed2_body (the control: its gathers and votes follow the digits).  In the device build the macro expands to nothing: the
-// shipped library has no recorder, no export for it, and k_msm_fixed2's instructions are what they were without it.
+// msm_fixed2_body (the control: its gathers and votes follow the digits).  The lane-per-(chunk, proof) functor of jobs of <= 64 proofs
+// (kernels.hpp K_msm_fixed_small) records its scalar loads too (MSM_TR_SCALAR, through the MSM_TRACE_F2 form: silent under f2_mute):
+// tests/test_verify_grouped.py counts them to tell the grouped verifier's path from the per-proof one.  In the device build the macro
+// expands to nothing: the shipped library has no recorder, no export for it, and k_msm_fixed2's instructions are what they were without it.
 #pragma once
 #include <stdint.h>
 
@@ -21,7 +23,7 @@ struct MsmTrace {
     int on = 0;
     uint64_t count[MSM_TR_KINDS] = {}, hash[MSM_TR_KINDS] = {};
     uint64_t ct_launches = 0, fixed2_launches = 0;   // counted whether or not the recorder is on
-    int f2_mute = 0;   // msm_fixed2_body's hooks are silent while set: a prove job sets it where its inner-product argument begins (outside
+    int f2_mute = 0;   // msm_fixed2_body's hooks (and K_msm_fixed_small's) are silent while set: a prove job sets it where its inner-product argument begins (outside
                        // the contract: l and r differ from batch to batch in either mode), so that the control recording is of the commit phase
 };
 inline MsmTrace& msm_trace() {

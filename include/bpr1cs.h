@@ -146,7 +146,8 @@ int bpr1cs_gens_point(const bpr1cs_gens* g, int which, uint32_t i, uint8_t out[3
 int bpr1cs_gens_table_info(const bpr1cs_gens* g, uint32_t* window_bits, uint32_t* windows, uint32_t* format, uint64_t* bytes);
 /* ---- options of a generator handle.  Every option has a default that is the measured optimum on MI355X (what bench.py runs);
  * value < 0 = back to that default.  No process-wide knobs exist: two threads on two handles never see each other's settings.
- * Results (proof bytes, verdicts) never depend on an option. */
+ * Results (proof bytes, verdicts) never depend on an option, with one exception: BPR1CS_OPT_VERIFY_GROUP_FALLBACK = 0 makes
+ * bpr1cs_verify_batch return one verdict per GROUP of proofs (see there). */
 #define BPR1CS_OPT_UNFOLD_ROUNDS 0    /* IPA rounds computed from the UN-folded generator tables before the folded generators are
                                          materialised (default: 4 - measured 2 / 3 / 4 / 5 = 2420 / 2748 / 2880 / 2678 proofs/s -, every round for a job of
                                          at most 64 proofs with N x proofs <= 655 360, where a variable-base round is pure latency; clamped to lg N) */
@@ -203,6 +204,29 @@ int bpr1cs_gens_table_info(const bpr1cs_gens* g, uint32_t* window_bits, uint32_t
                                          bytes as with 0.  Costs a second, narrow table set for all 2 + 2*cap bases (4-bit windows: 64 x 9
                                          slots x 128 B = 73.7 KB per base, 4.8 GB at capacity 32768), charged to the handle before W and the
                                          job size are chosen, and 64 instead of 23 additions per term over plain n-term sums */
+#define BPR1CS_OPT_VERIFY_GROUP 12    /* proofs per group G of bpr1cs_verify_batch's grouped form.  Default 0; 0 and 1 = off (one mega-check
+                                         per proof, 2N x windows table additions each); 2 .. 4096 (larger values are clamped) = the batch is
+                                         cut into ceil(batch / G) groups of G consecutive proofs (the last may be short; G >= batch is one
+                                         group), every group is checked by ONE combined identity test with per-proof weights - the
+                                         shared-base sum is then 2N x windows additions per GROUP - and only the proofs of a group
+                                         whose test fails are checked one by one.  Same verdicts as with 0 (an accepted group: every
+                                         proof of it is valid but with probability <= 1/l over the weights, l the group order).  A
+                                         call with batch = 1 takes the per-proof path.  Meant for groups of tens to a few hundred proofs
+                                         (measured: 16 / 64 / 256): a group's own points are summed by ONE wavefront, so
+                                         a group of thousands is a long serial chain - for one verdict over a whole large batch use
+                                         bpr1cs_verify_batch_combined.  bpr1cs_verify_batch_combined, _scalars and
+                                         _sharded ignore the option.
+                                         SECURITY: the weights come from the derivation of bpr1cs_verify_batch_combined, seeded with
+                                         the FIRST proof's 32 bytes of `verifier_rng_seeds` (index_base 0) and bound to every proof and
+                                         commitment of the batch: with fresh per-proof seeds they are unpredictable to whoever made
+                                         the proofs, as they are there; with `verifier_rng_seeds` = NULL (32 zero bytes) they are
+                                         deterministic Fiat-Shamir values of the digest over every proof and commitment - the caveat
+                                         that stands there for a constant batch seed */
+#define BPR1CS_OPT_VERIFY_GROUP_FALLBACK 13 /* what the grouped form does with a group whose identity test fails or that holds a malformed
+                                         proof.  1 (default): its proofs are re-checked by the per-proof path - the verdicts are those of
+                                         BPR1CS_OPT_VERIFY_GROUP = 0.  0: no re-check, every proof of such a group gets verdict 0 (for a
+                                         caller that rejects a whole submission unit anyway; the one setting under which verdicts depend
+                                         on an option).  Without effect while BPR1CS_OPT_VERIFY_GROUP is off */
 int bpr1cs_gens_set_option(bpr1cs_gens* g, int option, int value);
 /* bpr1cs_gens_create with options: `pairs` = n_pairs x (option, value).  BPR1CS_ERR_INVALID_ARGUMENT for an unknown option. */
 int bpr1cs_gens_create_opts(uint32_t gens_capacity, const int32_t* pairs, size_t n_pairs, bpr1cs_gens** out);
@@ -287,7 +311,10 @@ int bpr1cs_prove_batch_end(bpr1cs_job* job, uint8_t* proofs_out, uint8_t* commit
  * multiplication; ok_out[i] = 1 iff proof i is accepted (R1CSError::VerificationError / FormatError -> 0).
  *   proofs               batch * bpr1cs_proof_len(c)
  *   commitments          batch * m * 32   the V's the verifier `commit`s, in gadget order
- *   verifier_rng_seeds   batch * 32 or NULL (zeros): the 32 bytes upstream draws from thread_rng() for `r` */
+ *   verifier_rng_seeds   batch * 32 or NULL (zeros): the 32 bytes upstream draws from thread_rng() for `r`
+ * On a handle with BPR1CS_OPT_VERIFY_GROUP = G >= 2 a batch of 2 or more proofs is checked group by group - one combined identity
+ * test per G consecutive proofs, the per-proof check only inside a group that fails: per-proof verdicts at close to the cost of
+ * bpr1cs_verify_batch_combined while the proofs are good (see the option for the weights and BPR1CS_OPT_VERIFY_GROUP_FALLBACK). */
 int bpr1cs_verify_batch(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,
                         const uint8_t* proofs, const uint8_t* commitments, const uint8_t* verifier_rng_seeds, size_t batch,
                         int* ok_out);
@@ -305,7 +332,7 @@ int bpr1cs_verify_batch(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uin
  * over several GPUs gives every rank a disjoint `index_base` range, gathers the ranks' points (RCCL all_gather of
  * 32 bytes per rank, see bulletproofs-r1cs-gadgets_amd/sharding.py) and accepts iff bpr1cs_points_sum of them is the
  * identity (32 zero bytes) and every rank was well-formed.  A failing batch is then re-checked with
- * bpr1cs_verify_batch to find the culprit. */
+ * bpr1cs_verify_batch to find the culprit (BPR1CS_OPT_VERIFY_GROUP does both in one call on one device). */
 int bpr1cs_verify_batch_combined(const bpr1cs_gens* gens, const bpr1cs_circuit* circuit, const uint8_t* label, size_t label_len,
                                  const uint8_t* proofs, const uint8_t* commitments, const uint8_t* verifier_rng_seeds,
                                  const uint8_t* batch_seed /* 32 */, uint64_t index_base, size_t batch,

@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""Rates of the three device verifiers on one job of depth-32 tree proofs (the c4 workload): bpr1cs_verify_batch per proof, the same
+call grouped (BPR1CS_OPT_VERIFY_GROUP) and bpr1cs_verify_batch_combined.  One process, one generator handle per
+configuration (one at a time: the W = 11 tables take 198 GB), warm-up calls before the timed ones, every timed call ends in the
+library's own device synchronise.  One JSON line per row, proofs/s of every timed call.
+
+  python tools/verify_group_probe.py [--proofs 4096] [--reps 5] [--warm 2] [--rows a,b,c,d] [--groups 16,64,256] [--root DIR]
+
+rows: a = verify_batch, options at their defaults; b = grouped, G = 16 / 64 / 256, all proofs valid; c = G = 64 with one bad proof
+and with 1 % bad proofs in distinct groups; d = verify_batch_combined.  --root: import the package from another checkout (a build of
+the parent commit: row a there is the baseline of row a here - run both in one session, alternating)."""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--proofs", type=int, default=4096)
+ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--warm", type=int, default=2)
+ap.add_argument("--rows", default="a,b,c,d")
+ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ap.add_argument("--groups", default="16,64,256", help="the G of row b")
+ap.add_argument("--tag", default="")
+args = ap.parse_args()
+sys.path.insert(0, os.path.abspath(args.root))
+bp = importlib.import_module("bulletproofs-r1cs-gadgets_amd")
+wl = importlib.import_module("bulletproofs-r1cs-gadgets_amd.workloads")
+lib = bp.load_library(); bp.load_gadgets_library()
+if lib.bpr1cs_device_count() < 1:
+    raise SystemExit("verify_group_probe.py: no device (there is nothing to measure without one)")
+rows = set(args.rows.split(","))
+B, CAP = args.proofs, 32768
+w = wl.vsmt4(bp, None, 32, B, B, 0)
+circ = bp.CompiledGadget(w["gadget"], w["ip"], w["sp"])
+plen, m = circ.proof_len, w["m"]
+
+
+def tamper(P, positions):
+    P = list(P)
+    for i in positions:
+        b = bytearray(P[i]); b[1 + 8 * 32 + 3] ^= 1; P[i] = bytes(b)   # the scalar t_x
+    return P
+
+
+def timed(row, what, fn, check):
+    for _ in range(args.warm):
+        check(fn())
+    rates = []
+    for _ in range(args.reps):
+        t0 = time.perf_counter()
+        res = fn()
+        rates.append(B / (time.perf_counter() - t0))
+        check(res)
+    s = sorted(rates)
+    print(json.dumps({"row": row, "what": what, "tag": args.tag, "proofs": B, "proofs_per_s": [round(r, 1) for r in rates],
+                      "median": round(s[len(s) // 2], 1), "min": round(s[0], 1), "max": round(s[-1], 1)}), flush=True)
+
+
+def done(g):
+    g.close()
+    lib.bpr1cs_release_cached_memory()
+
+
+gens = bp.Gens(CAP)
+P, C = bp.prove_batch(gens, circ, w["label"], w["values"], w["blindings"], w["seeds"], B, wires=None)
+gens.release_scratch()
+pf, cm = b"".join(P), b"".join(b"".join(c) for c in C)
+
+
+def expect(want):
+    def check(got):
+        assert got == want, "verdicts differ: %d accepted, %d expected" % (sum(got), sum(want))
+    return check
+
+
+if "a" in rows:
+    timed("a", "verify_batch, default options", lambda: bp.verify_batch(gens, circ, w["label"], pf, cm, B), expect([True] * B))
+if "d" in rows:
+    timed("d", "verify_batch_combined", lambda: bp.verify_batch_combined(gens, circ, w["label"], pf, cm, B),
+          lambda r: (r[0] == bytes(32) and r[1]) or sys.exit("combined check failed"))
+done(gens)
+for G in sorted({int(x) for x in args.groups.split(",")} | ({64} if "c" in rows else set())):
+    if "b" not in rows and not (G == 64 and "c" in rows):
+        continue
+    g = bp.Gens(CAP, verify_group=G)
+    if "b" in rows:
+        timed("b", "verify_batch, verify_group=%d, all valid" % G, lambda: bp.verify_batch(g, circ, w["label"], pf, cm, B), expect([True] * B))
+    if G == 64 and "c" in rows:
+        one = [B // 4 + 5]
+        pb = b"".join(tamper(P, one))
+        timed("c", "verify_batch, verify_group=64, 1 bad proof", lambda: bp.verify_batch(g, circ, w["label"], pb, cm, B),
+              expect([i not in one for i in range(B)]))
+        many = sorted({(64 * k + (7 * k) % 64) % B for k in range(max(1, B // 100))})    # 1 %, one per group
+        pb = b"".join(tamper(P, many))
+        timed("c", "verify_batch, verify_group=64, %d bad proofs in %d groups" % (len(many), len({i // 64 for i in many})),
+              lambda: bp.verify_batch(g, circ, w["label"], pb, cm, B), expect([i not in set(many) for i in range(B)]))
+    done(g)
