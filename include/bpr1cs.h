@@ -320,9 +320,18 @@ int bpr1cs_verify_batch(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uin
                         int* ok_out);
 
 /* Cross-proof batched verification (SURVEY §8a P10 "batchable across proofs", §8e; the reference verifies one proof
- * at a time, gadget_vsmt_4.rs:479).  With weights rho_j = Merlin("bpr1cs batch verify", seed, index_base + j) the
- * `batch` mega-checks collapse into one: the 2N+2 shared bases B, B~, G_i, H_i get ONE combined scalar each
- * (sum_j rho_j * scalar_j) and a single fixed-base MSM; only the proofs' own points are handled per proof.
+ * at a time, gadget_vsmt_4.rs:479).  With per-proof weights rho_j the `batch` mega-checks collapse into one: the 2N+2
+ * shared bases B, B~, G_i, H_i get ONE combined scalar each (sum_j rho_j * scalar_j) and a single fixed-base MSM; only
+ * the proofs' own points are handled per proof.  The weights, in Merlin transcripts (<- appends, u64 = 8 bytes LE):
+ *   bind_j  = the proof's own verifier transcript after its last inner-product challenge, cloned,
+ *             <- ("ipp_a", a) <- ("ipp_b", b); challenge_bytes("bpr1cs-bind", 32)   (every byte of proof and commitments)
+ *   leaf_g  = Transcript("bpr1cs batch leaf") <- u64("leaf", g) <- ("proof", bind_j) for the 32 proofs j = 32g .. 32g+31
+ *             (the last leaf may be short); challenge_bytes("leaf", 32)
+ *   D       = Transcript("bpr1cs batch verify") <- ("seed", batch_seed) <- u64("base", index_base) <- u64("count", batch)
+ *             <- ("leaf", leaf_g) for every leaf in order; challenge_bytes("digest", 32)
+ *   rho_j   = Transcript("bpr1cs batch weight") <- ("digest", D) <- u64("j", index_base + j); challenge_scalar("rho")
+ * (csrc/kernels.hpp K_verify_transcript, K_batch_leaf, K_batch_digest, K_batch_weights; tests/verify_scalar_cases.py holds the
+ * same derivation over the oracle's Merlin and checks the combined scalars against it byte for byte.)
  * SECURITY: `batch_seed` must be 32 bytes of FRESH SECRET randomness drawn by the verifier after the proofs were
  * received (e.g. getrandom); the weights are derived from it together with a binding value of every proof and
  * commitment of the batch, so they cannot be predicted by whoever produced the proofs.  A public or constant seed
