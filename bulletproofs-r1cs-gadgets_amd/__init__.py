@@ -63,6 +63,8 @@ OPT_MSM_THREADS_LOG2, OPT_JOB_PROOFS, OPT_JOBS_IN_FLIGHT, OPT_HOST_CHAIN_PROOFS,
 OPT_HOST_CHAIN_SHARE = 10
 OPT_SECRET_INDEPENDENT = 11   # creation only: the commit phase through k_msm_fixed_ct
 OPT_VERIFY_GROUP, OPT_VERIFY_GROUP_FALLBACK = 12, 13   # verify_batch: one combined check per group of proofs, re-check of a failing group
+# values of OPT_VERIFY_GROUP_FALLBACK: a failing group's proofs all get verdict 0 / are re-checked one by one / are bisected on the device
+VERIFY_GROUP_FALLBACK_NONE, VERIFY_GROUP_FALLBACK_RECHECK, VERIFY_GROUP_FALLBACK_BISECT = 0, 1, 2
 OPTIONS = dict(unfold=OPT_UNFOLD_ROUNDS, witness_team=OPT_WITNESS_TEAM, tail_rounds=OPT_TAIL_ROUNDS, shared_back=OPT_SHARED_BACK,
                factor_vectors=OPT_FACTOR_VECTORS, msm_threads_log2=OPT_MSM_THREADS_LOG2, job_proofs=OPT_JOB_PROOFS,
                jobs_in_flight=OPT_JOBS_IN_FLIGHT, host_chain_proofs=OPT_HOST_CHAIN_PROOFS, window_bits=OPT_WINDOW_BITS,

@@ -53,7 +53,7 @@ struct BpOpts {
     std::atomic<int> host_chain{-1};       // jobs of up to this many proofs run their TranscriptRng chains on host threads (-1: 4 per usable CPU; 0: never)
     std::atomic<int> host_chain_share{-1}; // percent of a larger job's chains streamed from host threads (-1: 100 for a job that follows another of its call, with AVX-512)
     std::atomic<int> verify_group{0};      // proofs per group of bpr1cs_verify_batch's grouped form (0, 1: off - one mega-check per proof)
-    std::atomic<int> verify_group_fallback{1};  // 1: the proofs of a failing group are re-checked one by one, 0: they all get verdict 0
+    std::atomic<int> verify_group_fallback{1};  // 1: the proofs of a failing group are re-checked one by one, 0: they all get verdict 0, 2: the culprits are found by bisection on the device
     int window_bits = 0;                   // creation only (0: from the free memory)
     int secret_independent = 0;            // creation only: 1 = the commit phase runs through k_msm_fixed_ct over a narrow table set of its own
 };
@@ -71,7 +71,7 @@ static bool opt_apply(BpOpts& o, int option, int value, bool creating) {
         case BPR1CS_OPT_HOST_CHAIN_PROOFS: o.host_chain = value < 0 ? -1 : value; return true;
         case BPR1CS_OPT_HOST_CHAIN_SHARE: o.host_chain_share = value < 0 ? -1 : (value > 100 ? 100 : value); return true;
         case BPR1CS_OPT_VERIFY_GROUP: o.verify_group = value < 0 ? 0 : (value > 4096 ? 4096 : value); return true;
-        case BPR1CS_OPT_VERIFY_GROUP_FALLBACK: o.verify_group_fallback = value < 0 ? 1 : (value ? 1 : 0); return true;
+        case BPR1CS_OPT_VERIFY_GROUP_FALLBACK: o.verify_group_fallback = value < 0 ? 1 : (value == BPR1CS_VERIFY_GROUP_FALLBACK_BISECT ? 2 : (value ? 1 : 0)); return true;
         case BPR1CS_OPT_WINDOW_BITS:
             if (!creating) return false;
             o.window_bits = value <= 0 ? 0 : (value < 4 ? 4 : (value > 15 ? 15 : value));   // (digits travel as sign + 15-bit magnitude: |d| <= 2^14 at W = 15)

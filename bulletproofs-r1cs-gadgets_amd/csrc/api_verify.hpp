@@ -344,6 +344,120 @@ static int verify_batch_grouped_once(const bpr1cs_gens* g, const bpr1cs_circuit*
     API_CATCH
 }
 
+// Bisection inside a failing group (BPR1CS_OPT_VERIFY_GROUP_FALLBACK = 2).  S(R) = sum_{b in R, fail[b] = 0} rho_b E_b is
+// additive over the proofs of a range R, and everything it is made of - gh, bsc, the weights, the weighted own points - is still on the
+// device when a group fails.  Level-synchronous: depth 0 tests the groups; every later depth takes the failing ranges of more than one
+// proof of ALL groups, computes S of their left halves (ceil(s / 2) proofs) with one range combination, one run_msm whose batch is the
+// number of ranges and one range finish - which also forms S(right) = S(parent) - S(left) - and reads the identity flags back.  A
+// passing range accepts its well-formed proofs, a failing range of one proof rejects it.  Nothing is uploaded again and the per-proof
+// path is not taken.
+struct BisectRange { uint32_t lo, hi, pt; };   // a failing range of more than one proof; pt: where its S sits among the depth's points
+static void launch_combine_ranges(uint32_t rows, const K_combine_scalars_ranges& f, dev_stream_t st) {
+    const uint32_t wgs = combine_grouped_wgs(rows, f.R);   // (the grid cap and the 32-bit output index of the grouped combination)
+    if (!wgs) return;
+#if !defined(BPR1CS_HOSTSIM)
+    hipLaunchKernelGGL(k_combine_scalars_range_wave, dim3(wgs), dim3(64), 0, st, f, rows * f.R);
+    HIPCHK(hipGetLastError());
+#else
+    launch((uint64_t)rows * f.R, f, st);
+#endif
+}
+static int verify_batch_bisect_once(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,
+                                    const uint8_t* proofs, const uint8_t* commitments, const uint8_t* verifier_rng_seeds, size_t batch,
+                                    uint32_t G, int* ok_out) {
+    if (!ok_out) return BPR1CS_ERR_INVALID_ARGUMENT;
+    int rc = verify_args_ok(g, c, label, proofs, commitments, batch);
+    if (rc) return rc;
+    API_TRY
+    dev_stream_t st = g->stream;
+    CallScope scope(st);
+    MsmStats stats;
+    VerifyCtx v;
+    verify_front(v, g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, true, st);
+    const uint32_t B = v.B, N = v.N, NG = (B + G - 1) / G, baseG = 2, baseH = 2 + g->cap;
+    uint8_t bseed[32] = {0};   // as verify_groups_device: the first proof's verifier seed
+    if (verifier_rng_seeds) memcpy(bseed, verifier_rng_seeds, 32);
+    CombinedCtx k;
+    verify_weights(k, v, bseed, 0, st);
+    // the own points first: a point that does not decode sets its proof's flag, and the sums below leave such a proof out
+    k.pts.alloc((size_t)v.P * B);
+    K_verify_points kp{v.d_pf.p, v.d_vc.p, v.chal.p, v.uk.p, v.wvec.p + (size_t)3 * v.n * B, k.pts.p, v.fail.p, B, v.m, v.lgN, (uint32_t)v.plen};
+    kp.rho = k.rho.p;
+    launch((uint64_t)v.P * B, kp, st);
+    // scratch of a slice of at most NG ranges - what depth 0 needs - shared by all depths
+    k.cgh.alloc((size_t)2 * N * NG); k.cb.alloc((size_t)2 * NG);
+    DevBuf<ge> rpts(NG), partial, spts[2];   // spts: S of the ranges of this depth and of the one before (the parents)
+    std::vector<BisectRange> cur(NG), next;
+    for (uint32_t grp = 0; grp < NG; grp++) cur[grp] = BisectRange{grp * G, std::min(B, (grp + 1) * G), 0};
+    std::vector<int> pfail(B), zero;
+    std::vector<uint32_t> h_rng;
+    for (uint32_t depth = 0; !cur.empty(); depth++) {
+        const uint32_t R = (uint32_t)cur.size();
+        h_rng.resize((size_t)3 * R);   // lo | hi | parent of the tested ranges: the groups at depth 0, the left halves below
+        for (uint32_t i = 0; i < R; i++) {
+            const uint32_t s = cur[i].hi - cur[i].lo;
+            h_rng[i] = cur[i].lo;
+            h_rng[R + i] = depth ? cur[i].lo + (s + 1) / 2 : cur[i].hi;
+            h_rng[2 * R + i] = cur[i].pt;
+        }
+        DevBuf<uint32_t> d_rng((size_t)3 * R);
+        dev_h2d(d_rng.p, h_rng.data(), h_rng.size() * sizeof(uint32_t), st);
+        DevBuf<ge>& out = spts[depth & 1];
+        const ge* parent = depth ? spts[(depth & 1) ^ 1].p : nullptr;
+        out.alloc((size_t)2 * R);   // left | right
+        DevBuf<int> d_zero((size_t)2 * R);
+        for (uint32_t off = 0; off < R; off += NG) {
+            const uint32_t cnt = std::min(NG, R - off);
+            const uint32_t *lo = d_rng.p + off, *hi = d_rng.p + R + off, *par = d_rng.p + 2 * (size_t)R + off;
+            launch_combine_ranges(2 * N, K_combine_scalars_ranges{v.gh.p, k.rho.p, v.fail.p, lo, hi, k.cgh.p, B, cnt}, st);
+            launch_combine_ranges(2, K_combine_scalars_ranges{v.bsc.p, k.rho.p, v.fail.p, lo, hi, k.cb.p, B, cnt}, st);
+            {
+                K_range_points kr{k.pts.p, v.fail.p, lo, hi, rpts.p, B, v.P};
+#if !defined(BPR1CS_HOSTSIM)
+                hipLaunchKernelGGL(k_range_points_wave, dim3(cnt), dim3(64), 0, st, kr);
+                HIPCHK(hipGetLastError());
+#else
+                launch(cnt, kr, st);
+#endif
+            }
+            MsmPlan plan;
+            MsmSeg sg{k.cgh.p, N, N, N, 0, baseG, 0}, sh{k.cgh.p + (size_t)N * cnt, N, N, N, 0, baseH, 0};
+            run_msm(g, sg, sh, cnt, partial, plan, st, &stats);
+            K_range_finish kf{g->tab.p, g->tc, partial.p, rpts.p, k.cb.p, parent, par, out.p + off, out.p + R + off,
+                              d_zero.p + off, d_zero.p + R + off, cnt, plan.nchunks};
+#if !defined(BPR1CS_HOSTSIM)
+            if (cnt <= FINISH_WAVE_MAX_PROOFS) {
+                hipLaunchKernelGGL(k_range_finish_wave, dim3(cnt), dim3(64), 0, st, kf);
+                HIPCHK(hipGetLastError());
+            } else
+#endif
+            launch(cnt, kf, st);
+        }
+        zero.resize((size_t)2 * R);
+        dev_d2h(zero.data(), d_zero.p, sizeof(int) * (depth ? 2 * (size_t)R : R), st);
+        if (depth == 0) {
+            dev_d2h(pfail.data(), v.fail.p, sizeof(int) * B, st);
+            for (uint32_t b = 0; b < B; b++) ok_out[b] = !pfail[b];   // a malformed proof is rejected and is part of no sum
+        }
+        next.clear();
+        auto classify = [&](uint32_t lo, uint32_t hi, uint32_t pt, int is_zero) {
+            if (is_zero) return;                        // every well-formed proof of the range is accepted
+            if (hi - lo == 1) ok_out[lo] = 0;           // (a range of one malformed proof sums to the identity: it never gets here)
+            else next.push_back(BisectRange{lo, hi, pt});
+        };
+        for (uint32_t i = 0; i < R; i++) {
+            if (depth == 0) { classify(cur[i].lo, cur[i].hi, i, zero[i]); continue; }
+            const uint32_t mid = h_rng[R + i];
+            classify(cur[i].lo, mid, i, zero[i]);
+            classify(mid, cur[i].hi, R + i, zero[R + i]);
+        }
+        cur.swap(next);
+    }
+    stats.collect();
+    return BPR1CS_OK;
+    API_CATCH
+}
+
 // Multi-GPU form of the batched verifier: instead of evaluating the shared-base MSM itself, a rank
 // returns its combined scalar vector; the ranks add their vectors (all_gather / all_reduce of 2N+2 scalars, ~2 MB at
 // N = 32768), each evaluates 1/world of the bases with bpr1cs_msm_fixed, and the points are gathered and summed.
@@ -412,7 +526,10 @@ extern "C" int bpr1cs_verify_batch(const bpr1cs_gens* g, const bpr1cs_circuit* c
                                    int* ok_out) {
     const int G = g ? g->opts.verify_group.load() : 0;
     if (G >= 2 && batch >= 2) {
-        const bool fallback = g->opts.verify_group_fallback.load() != 0;
+        const int mode = g->opts.verify_group_fallback.load();
+        if (mode == BPR1CS_VERIFY_GROUP_FALLBACK_BISECT)
+            return with_scratch_retry(g, [&] { return verify_batch_bisect_once(g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, (uint32_t)G, ok_out); });
+        const bool fallback = mode != BPR1CS_VERIFY_GROUP_FALLBACK_NONE;
         return with_scratch_retry(g, [&] { return verify_batch_grouped_once(g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, (uint32_t)G, fallback, ok_out); });
     }
     return with_scratch_retry(g, [&] { return verify_batch_once(g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, ok_out); });

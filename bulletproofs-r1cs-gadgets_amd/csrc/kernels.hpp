@@ -1860,6 +1860,76 @@ struct K_group_points {  // gid = grp : out[grp] = sum of the P weighted points 
         gfail[grp] = bad;
     }
 };
+// Bisection inside a failing group (BPR1CS_OPT_VERIFY_GROUP_FALLBACK = 2): the same two segmented sums over arbitrary ranges
+// [lo[r], hi[r]) of proofs - the groups themselves at level 0, the left halves of the failing ranges below - from which the malformed
+// proofs (fail[b] != 0) are left out: S(R) = sum_{b in R, fail[b] = 0} rho_b E_b is additive over proofs, so one MSM column per split
+// and a point subtraction give both children.  Wavefront forms: kernels_hip.hpp k_combine_scalars_range_wave, k_range_points_wave,
+// k_range_finish_wave.
+struct K_combine_scalars_ranges {  // gid = row*R + r : out[gid] = sum_{b in [lo[r], hi[r]), fail[b] = 0} in[row*B + b] * rho[b]   (forms as K_combine_scalars)
+    const sc* in;
+    const sc* rho;       // Montgomery
+    const int* fail;     // [B]
+    const uint32_t* lo;  // [R]
+    const uint32_t* hi;  // [R]
+    sc* out;             // [rows][R]
+    uint32_t B, R;
+    HD void operator()(uint32_t g) const {
+        const uint32_t row = g / R, r = g % R;
+        sc acc = sc_zero();
+        const sc* in_row = in + (size_t)row * B;
+        for (uint32_t b = lo[r]; b < hi[r]; b++)
+            if (!fail[b]) acc = sc_add(acc, sc_mul(in_row[b], rho[b]));
+        out[g] = acc;
+    }
+};
+struct K_range_points {  // gid = r : out[r] = sum of the P weighted points of every well-formed proof of the range
+    const ge* pts;       // [P][B]
+    const int* fail;     // [B]
+    const uint32_t* lo;  // [R]
+    const uint32_t* hi;  // [R]
+    ge* out;             // [R]
+    uint32_t B, P;
+    HD void operator()(uint32_t r) const {
+        ge acc = ge_identity();
+        for (uint32_t b = lo[r]; b < hi[r]; b++) {
+            if (fail[b]) continue;
+            for (uint32_t p = 0; p < P; p++) acc = ge_add_ge(acc, pts[(size_t)p * B + b]);
+        }
+        out[r] = acc;
+    }
+};
+struct K_range_finish {  // gid = r : S(left) of split r, S(right) = S(parent) - S(left), their identity flags
+    const uint8_t* tab;
+    TabCfg tc;
+    const ge* msm_partial;  // [nchunks][R]
+    const ge* rpts;         // [R]: own points of the range (K_range_points)
+    const sc* bsc;          // [2][R]
+    const ge* parent;       // S of the ranges that were split (nullptr at level 0: the range is a whole group, there is no right part)
+    const uint32_t* par;    // [R]: index of range r's parent in `parent`
+    ge* left;               // [R]
+    ge* right;              // [R]
+    int* zl;                // [R]: S(left) is the identity
+    int* zr;                // [R]: S(right) is the identity
+    uint32_t R, nchunks;
+    HD void operator()(uint32_t r) const {
+        ge acc = rpts[r];
+        for (uint32_t c = 0; c < nchunks; c++) acc = ge_add_ge(acc, msm_partial[(size_t)c * R + r]);
+        acc = table_mul_acc(acc, tab, sc_from_mont(bsc[r]), tc);
+        acc = table_mul_acc(acc, tab + tc.base_bytes(), sc_from_mont(bsc[(size_t)R + r]), tc);
+        left[r] = acc;
+        uint8_t enc[32];
+        int right_zero = 0;
+        if (parent) {
+            const ge rest = ge_sub(parent[par[r]], ge_to_cached(acc));
+            right[r] = rest;
+            ge_compress(rest, enc);
+            right_zero = bytes_are_zero32(enc);
+        }
+        ge_compress(acc, enc);
+        zl[r] = bytes_are_zero32(enc);
+        if (parent) zr[r] = right_zero;
+    }
+};
 struct K_batch_finish {  // single thread: sum of the partial sums -> compressed point, AND of the format checks
     const uint8_t* tab;
     TabCfg tc;

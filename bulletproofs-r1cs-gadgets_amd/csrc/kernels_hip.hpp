@@ -412,6 +412,89 @@ __global__ void __launch_bounds__(64) k_group_points_wave(K_group_points f) {
     }
 }
 
+// Bisection inside a failing group (BPR1CS_OPT_VERIFY_GROUP_FALLBACK = 2): the three wavefront forms of K_combine_scalars_ranges,
+// K_range_points and K_range_finish.  K_combine_scalars_ranges with a wavefront per (row, range): as k_combine_scalars_group_wave, with
+// the range's bounds read from lo[] / hi[] (the same for all lanes) and a malformed proof's term left out - lanes stay together
+// through the shuffles, a skipped lane adds zero.  Output g = row*R + r; the grid is capped the same way.
+__global__ void __launch_bounds__(64) k_combine_scalars_range_wave(K_combine_scalars_ranges f, uint32_t outputs) {
+    const uint32_t lane = threadIdx.x;
+    for (uint64_t g = blockIdx.x; g < outputs; g += gridDim.x) {
+        const uint32_t row = (uint32_t)g / f.R, r = (uint32_t)g % f.R;
+        const uint32_t lo = f.lo[r], hi = f.hi[r];
+        const sc* in_row = f.in + (size_t)row * f.B;
+        sc acc = sc_zero();
+        for (uint32_t b = lo + lane; b < hi; b += 64u)
+            if (!f.fail[b]) acc = sc_add(acc, sc_mul(in_row[b], f.rho[b]));
+#pragma unroll 1
+        for (int sft = 32; sft > 0; sft >>= 1) {
+            sc o;
+#pragma unroll
+            for (int i = 0; i < 8; i++) o.v[i] = (uint32_t)__shfl_xor((int)acc.v[i], sft, 64);
+            acc = sc_add(acc, o);
+        }
+        if (lane == 0) f.out[g] = acc;
+    }
+}
+// K_range_points with a wavefront per range: items (p, j) -> pts[p*B + lo + j] as in k_group_points_wave, those of a malformed proof skipped
+__global__ void __launch_bounds__(64) k_range_points_wave(K_range_points f) {
+    const uint32_t r = blockIdx.x, lane = threadIdx.x;
+    const uint32_t lo = f.lo[r], hi = f.hi[r], cnt = hi - lo;
+    ge acc = ge_identity();
+    for (uint32_t idx = lane; idx < cnt * f.P; idx += 64u) {
+        const uint32_t p = idx / cnt, j = idx - p * cnt;
+        if (!f.fail[lo + j]) acc = ge_add_ge(acc, f.pts[(size_t)p * f.B + lo + j]);
+    }
+#pragma unroll 1
+    for (int sft = 32; sft > 0; sft >>= 1) acc = ge_add_ge(acc, ge_shfl_xor(acc, sft));
+    if (lane == 0) f.out[r] = acc;
+}
+// K_range_finish with a wavefront per range (a depth's handful of ranges): table entries, chunk sums and the range's own-point sum are
+// items as in k_verify_finish_wave; after the butterfly every lane holds S(left), so every lane forms S(right) = S(parent) - S(left)
+// and the two compressions share the wavefront's power; lane 0 stores the points, then the flags.
+__global__ void __launch_bounds__(64) k_range_finish_wave(K_range_finish f) {
+    const uint32_t r = blockIdx.x, lane = threadIdx.x;
+    const TabCfg tc = f.tc;
+    const uint32_t n_tab = 2u * tc.windows, n_items = n_tab + f.nchunks + 1u;
+    const sc e1 = sc_from_mont(f.bsc[r]), e2 = sc_from_mont(f.bsc[(size_t)f.R + r]);
+    ge acc = ge_identity();
+    bool table_class = false;
+    for (uint32_t idx = lane; idx < n_items; idx += 64u) {   // (per lane: table items first - the enumeration puts them first)
+        if (idx < n_tab) {
+            const uint32_t t = idx / tc.windows, k = idx % tc.windows;
+            const sc s = t ? e2 : e1;
+            int carry = 0, d = 0;
+            for (uint32_t kk = 0; kk <= k; kk++) d = tab_digit(s, kk, carry, tc);
+            if (d != 0) {
+                const int neg = d < 0;
+                const uint32_t mag = (uint32_t)(neg ? -d : d);
+                acc = ge_madd_t(acc, ge_niels_load(f.tab + (size_t)t * tc.base_bytes() + ((size_t)k * tc.row + mag) * tc.stride), neg);
+                table_class = true;
+            }
+        } else {
+            if (table_class) { acc = ge_from_table_class(acc); table_class = false; }
+            const uint32_t c = idx - n_tab;
+            acc = ge_add_ge(acc, c < f.nchunks ? f.msm_partial[(size_t)c * f.R + r] : f.rpts[r]);
+        }
+    }
+    if (table_class) acc = ge_from_table_class(acc);
+#pragma unroll 1
+    for (int sft = 32; sft > 0; sft >>= 1) acc = ge_add_ge(acc, ge_shfl_xor(acc, sft));
+    if (lane == 0) f.left[r] = acc;
+    uint8_t enc[32];
+    int right_zero = 0;
+    if (f.parent) {   // (uniform over the launch)
+        const ge rest = ge_sub(f.parent[f.par[r]], ge_to_cached(acc));
+        if (lane == 0) f.right[r] = rest;
+        ge_compress_t(rest, enc, fe_pow_wave{});
+        right_zero = bytes_are_zero32(enc);
+    }
+    ge_compress_t(acc, enc, fe_pow_wave{});
+    if (lane == 0) {
+        f.zl[r] = bytes_are_zero32(enc);
+        if (f.parent) f.zr[r] = right_zero;
+    }
+}
+
 // K_msm_fixed_small with the first level of its reduction tree inside the wavefront: workgroup (request r, proof b, group w) sums the
 // 64 chunks w*64 .. w*64+63 of proof b - a lane each - and folds them with the shuffle butterfly: partial[w*B + b].  One or two requests
 // per launch (L_k and R_k of an IPA round): for ONE proof a round is then a launch of 2 x nchunks/64 wavefronts and one K_ge_reduce per side

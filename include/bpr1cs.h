@@ -226,7 +226,24 @@ int bpr1cs_gens_table_info(const bpr1cs_gens* g, uint32_t* window_bits, uint32_t
                                          proof.  1 (default): its proofs are re-checked by the per-proof path - the verdicts are those of
                                          BPR1CS_OPT_VERIFY_GROUP = 0.  0: no re-check, every proof of such a group gets verdict 0 (for a
                                          caller that rejects a whole submission unit anyway; the one setting under which verdicts depend
-                                         on an option).  Without effect while BPR1CS_OPT_VERIFY_GROUP is off */
+                                         on an option).  2: bisection on the device - same verdicts as 1, without the per-proof path.
+                                         For a range R of proofs of one group let S(R) be the sum of rho_b x (proof b's mega-check
+                                         point) over the well-formed proofs b of R.  A malformed proof (its format check or the
+                                         decoding of one of its points fails) is part of no sum and gets verdict 0.  S(R) = identity:
+                                         every well-formed proof of R gets 1.  A failing range of one proof: that proof gets 0.  A
+                                         failing range of s > 1 proofs is split into its first ceil(s / 2) proofs and the rest:
+                                         S(left) is computed - one column of the shared-base sum plus left's own points -,
+                                         S(right) = S(R) - S(left) is a point subtraction, and both parts are treated the same way.
+                                         The failing ranges of all groups at one depth share their launches (at most
+                                         ceil(log2 G) <= 12 depths); a group with k bad proofs costs about k x ceil(log2 G) columns
+                                         where 1 costs G, and a group whose only fault is a malformed proof costs nothing more.
+                                         SECURITY: the sub-range tests reuse the group's weights rho_b, which were fixed after every
+                                         proof of the batch was bound into the digest: a tested range that holds an invalid proof is
+                                         accepted with probability <= 1/l, and the bound for a call is (number of ranges tested)/l.
+                                         Values above 2 mean 1.  Without effect while BPR1CS_OPT_VERIFY_GROUP is off */
+#define BPR1CS_VERIFY_GROUP_FALLBACK_NONE 0    /* values of BPR1CS_OPT_VERIFY_GROUP_FALLBACK */
+#define BPR1CS_VERIFY_GROUP_FALLBACK_RECHECK 1
+#define BPR1CS_VERIFY_GROUP_FALLBACK_BISECT 2
 int bpr1cs_gens_set_option(bpr1cs_gens* g, int option, int value);
 /* bpr1cs_gens_create with options: `pairs` = n_pairs x (option, value).  BPR1CS_ERR_INVALID_ARGUMENT for an unknown option. */
 int bpr1cs_gens_create_opts(uint32_t gens_capacity, const int32_t* pairs, size_t n_pairs, bpr1cs_gens** out);

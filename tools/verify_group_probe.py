@@ -4,10 +4,13 @@ call grouped (BPR1CS_OPT_VERIFY_GROUP) and bpr1cs_verify_batch
 configuration (one at a time: the W = 11 tables take 198 GB), warm-up calls before the timed ones, every timed call ends in the
 library's own device synchronise.  One JSON line per row, proofs/s of every timed call.
 
-  python tools/verify_group_probe.py [--proofs 4096] [--reps 5] [--warm 2] [--rows a,b,c,d] [--groups 16,64,256] [--root DIR]
+  python tools/verify_group_probe.py [--proofs 4096] [--reps 5] [--warm 2] [--rows a,b,c,d] [--groups 16,64,256] [--fallback 1,2,1]
+                                     [--root DIR]
 
 rows: a = verify_batch, options at their defaults; b = grouped, G = 16 / 64 / 256, all proofs valid; c = G = 64 with one bad proof
-and with 1 % bad proofs in distinct groups; d = verify_batch_combined.  --root: import the package from another checkout (a build of
+and with 1 % bad proofs in distinct groups; d = verify_batch_combined.  --fallback: the values of BPR1CS_OPT_VERIFY_GROUP_FALLBACK that
+rows b and c run with, one after the other on one handle (1 = re-check of a failing group, 2 = bisection; "1,2,1" alternates and gives
+the spread of the rows with 1; default: the option is left alone).  --root: import the package from another checkout (a build of
 the parent commit: row a there is the baseline of row a here - run both in one session, alternating)."""
 import argparse
 import importlib
@@ -23,6 +26,7 @@ ap.add_argument("--warm", type=int, default=2)
 ap.add_argument("--rows", default="a,b,c,d")
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument("--groups", default="16,64,256", help="the G of row b")
+ap.add_argument("--fallback", default="", help="values of BPR1CS_OPT_VERIFY_GROUP_FALLBACK for rows b and c, in order (default: not set)")
 ap.add_argument("--tag", default="")
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.root))
@@ -86,15 +90,20 @@ for G in sorted({int(x) for x in args.groups.split(",")} | ({64} if "c" in rows 
     if "b" not in rows and not (G == 64 and "c" in rows):
         continue
     g = bp.Gens(CAP, verify_group=G)
-    if "b" in rows:
-        timed("b", "verify_batch, verify_group=%d, all valid" % G, lambda: bp.verify_batch(g, circ, w["label"], pf, cm, B), expect([True] * B))
-    if G == 64 and "c" in rows:
-        one = [B // 4 + 5]
-        pb = b"".join(tamper(P, one))
-        timed("c", "verify_batch, verify_group=64, 1 bad proof", lambda: bp.verify_batch(g, circ, w["label"], pb, cm, B),
-              expect([i not in one for i in range(B)]))
-        many = sorted({(64 * k + (7 * k) % 64) % B for k in range(max(1, B // 100))})    # 1 %, one per group
-        pb = b"".join(tamper(P, many))
-        timed("c", "verify_batch, verify_group=64, %d bad proofs in %d groups" % (len(many), len({i // 64 for i in many})),
-              lambda: bp.verify_batch(g, circ, w["label"], pb, cm, B), expect([i not in set(many) for i in range(B)]))
+    for fb in [int(x) for x in args.fallback.split(",")] if args.fallback else [None]:
+        sfx = ""
+        if fb is not None:
+            g.set_option("verify_group_fallback", fb)
+            sfx = ", fallback=%d" % fb
+        if "b" in rows:
+            timed("b", "verify_batch, verify_group=%d, all valid%s" % (G, sfx), lambda: bp.verify_batch(g, circ, w["label"], pf, cm, B), expect([True] * B))
+        if G == 64 and "c" in rows:
+            one = [B // 4 + 5]
+            pb = b"".join(tamper(P, one))
+            timed("c", "verify_batch, verify_group=64, 1 bad proof%s" % sfx, lambda: bp.verify_batch(g, circ, w["label"], pb, cm, B),
+                  expect([i not in one for i in range(B)]))
+            many = sorted({(64 * k + (7 * k) % 64) % B for k in range(max(1, B // 100))})    # 1 %, one per group
+            pb = b"".join(tamper(P, many))
+            timed("c", "verify_batch, verify_group=64, %d bad proofs in %d groups%s" % (len(many), len({i // 64 for i in many}), sfx),
+                  lambda: bp.verify_batch(g, circ, w["label"], pb, cm, B), expect([i not in set(many) for i in range(B)]))
     done(g)
