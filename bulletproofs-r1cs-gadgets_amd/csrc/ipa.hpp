@@ -29,12 +29,13 @@ struct IpaIO {
     // optional: the last `tail_rounds` rounds (latency bound: a few wavefronts per proof, ~10 dependent launches per round)
     // go to `tail_stream`, which waits for the heavy stream at the hand-off; the heavy stream is then free for the next
     // job's sums while this job's tail finishes next to them.  At the hand-off the live state (the 2 m_k scalars of a and b,
-    // the 2 m_k generators per side, lambda^-1) is COPIED into buffers of the job's own (`tail_keep`) and the shared arena is
+    // the 2 m_k generators per side, lambda^-1, the y^-1 powers of the H side's position factor) is COPIED into buffers of the job's own (`tail_keep`) and the shared arena is
     // left: the tail never touches memory the next job's back phase may already be writing, so that job does not wait for it.
     dev_stream_t tail_stream{};
     uint32_t tail_rounds = 0;
     struct TailKeep {  // owned by the job: lives until it is released
         DevBuf<sc> a, bb, linv, cross, cpart;
+        DevBuf<sc> ypow;   // unit form of the first fold: the entries of the y^-1 power tables the tail's positions reach (YPos)
         DevBuf<ge> GH, vwin, vsum, vout;
         DevBuf<ge_cached> vtab;
         DevBuf<uint32_t> vdig;
@@ -85,9 +86,12 @@ static IpaEnd enqueue_ipa(const IpaIO& io, dev_stream_t st, MsmStats* stats) {
     // MsmGeo, csrc/msm_kernel.hpp) for launches of the shipped kernel, which then need no N x B scalar arrays at all
     const bool fused = geo && B > MSM_LANE_PATH_MAX_PROOFS && io.fuse_scalars;
     MsmGeo mg;
+    auto geo_fac = [&](uint32_t k) {
+        launch((uint64_t)2 * (k ? 1u << (k - 1) : 1u) * B, K_ipa_fac{fac.p, k ? io.uk + (size_t)(k - 1) * 2 * B : nullptr, io.geo.upad, B, k, facT}, st);
+    };
     auto geo_scalars = [&](uint32_t k, const sc* va, const sc* vb) {
         const uint32_t lgNk = lgN - k;
-        launch((uint64_t)2 * (k ? 1u << (k - 1) : 1u) * B, K_ipa_fac{fac.p, k ? io.uk + (size_t)(k - 1) * 2 * B : nullptr, io.geo.upad, B, k, facT}, st);
+        geo_fac(k);
         const sc* hfp = nullptr;
         if (lgNk >= 8 && hfJ) {
             launch((uint64_t)2 * hfJ * B, K_ipa_hf{fac.p, io.geo.phi + (size_t)io.geo.H * B, hf.p, B, hfJ, lgNk - 8, facT}, st);
@@ -105,6 +109,13 @@ static IpaEnd enqueue_ipa(const IpaIO& io, dev_stream_t st, MsmStats* stats) {
                                  // quarter of the window-sum buffer, of which every job slot holds a copy
     // variable-base rounds come in pairs on one set of multiples, generators folded two levels at a time (K_ipa_vb_dig2 / _fold2)
     bool vb_reuse = false;
+    // The first fold in its unit form (kernels.hpp, K_ipa_fold_scal): jobs of the shipped MSM kernel whose factors have the closed form.
+    // Jobs of up to MSM_LANE_PATH_MAX_PROOFS proofs (K_ipa_fold_from_tables) and factor VECTORS (bpr1cs_ipa_create, the measuring knob)
+    // keep all 2^r terms with linv = 1 and no position factor - the same points, so the same bytes.
+    const bool unit = geo && r >= 1 && r < lgN && B > MSM_LANE_PATH_MAX_PROOFS && io.geo.n1 >= M;
+    YPos ypos;
+    DevBuf<sc> fsc;
+    DevBuf<uint32_t> fidx;
     auto finisher = [&](const ge* part, uint32_t nch, const sc* c, uint8_t* out) {
         K_msm_finish f{g->tab.p, g->tc, part, c, io.qw, out, B, nch, 0};
         if (io.qpt) { f.extra2 = nullptr; f.extra_pt = io.qpt; }
@@ -133,6 +144,12 @@ static IpaEnd enqueue_ipa(const IpaIO& io, dev_stream_t st, MsmStats* stats) {
                 T.GH.alloc((size_t)2 * Nk * B);
                 T.vtab.alloc((size_t)VB_MULT * 4 * mk * B); T.vdig.alloc((size_t)VB_WORDS * 4 * mk * B);
                 T.vwin.alloc((size_t)2 * VB_WINDOWS * VC_TAIL * B); T.vsum.alloc((size_t)2 * VB_WINDOWS * B); T.vout.alloc((size_t)2 * B);
+                if (ypos.lo) T.ypow.alloc((size_t)(256 + std::max<uint32_t>(Nk >> 8, 1u)) * B);
+            }
+            if (ypos.lo) {  // positions below Nk from here on: the low table and the first Nk / 256 entries of the high one
+                dev_d2d(T.ypow.p, ypos.lo, (size_t)256 * B * sizeof(sc), st);
+                dev_d2d(T.ypow.p + (size_t)256 * B, ypos.hi, (size_t)std::max<uint32_t>(Nk >> 8, 1u) * B * sizeof(sc), st);
+                ypos.lo = T.ypow.p; ypos.hi = T.ypow.p + (size_t)256 * B;
             }
             dev_d2d(T.a.p, a, (size_t)Nk * B * sizeof(sc), st);
             dev_d2d(T.bb.p, bb, (size_t)Nk * B * sizeof(sc), st);
@@ -223,7 +240,17 @@ static IpaEnd enqueue_ipa(const IpaIO& io, dev_stream_t st, MsmStats* stats) {
                     vdigp = vdig.p; vwinp = vwin.p;
                 }
                 const sc* fG = cG; const sc* fH = cH;   // scalars of the folded generators: Montgomery factor vectors, or ...
-                if (geo) {  // ... their closed form, written out once (canonical) where the product scalars of the rounds before lived
+                if (unit) {
+                    // ... or, in the unit form, the 2 x 2^r x 2 ratios to the coefficient of block 0 (per proof; x 2: the padding flag), which the
+                    // launch takes as a plain canonical vector through a term -> scalar index list; linv starts at that coefficient
+                    geo_fac(k);
+                    fsc.alloc((size_t)4 * facT * B);
+                    fidx.alloc((size_t)N - M);
+                    linv.alloc((size_t)2 * B);
+                    launch((uint64_t)2 * facT * B, K_ipa_fold_scal{fac.p, io.uk, io.geo.plo + (size_t)256 * B, io.geo.phi + (size_t)io.geo.H * B, fsc.p, linv.p, B, facT, r, M}, st);
+                    launch((uint64_t)N - M, K_ipa_fold_idx{fidx.p, M, io.geo.n1}, st);
+                    ypos.lo = io.geo.plo + (size_t)256 * B; ypos.hi = io.geo.phi + (size_t)io.geo.H * B;
+                } else if (geo) {  // ... their closed form, written out once (canonical) where the product scalars of the rounds before lived
                     geo_scalars(k, nullptr, nullptr);
                     fG = sGp; fH = sHp;
                 }
@@ -238,20 +265,29 @@ static IpaEnd enqueue_ipa(const IpaIO& io, dev_stream_t st, MsmStats* stats) {
                     const MsmSeg none{nullptr, 0, 1, 1, 0, 0, 0};
                     L.job[0] = MsmJob{{MsmSeg{fG, N, N, N, 0, baseG, f_mont}, none}, g->tab.p, g->tc, GHp, N / M, M, 1};
                     L.job[1] = MsmJob{{MsmSeg{fH, N, N, N, 0, baseH, f_mont}, none}, g->tab.p, g->tc, GHp + (size_t)M * B, N / M, M, 1};
-                    if (fused) {   // the factors themselves, produced at the term fetch (no vector)
+                    uint32_t per_side = N;
+                    if (unit) {   // terms t >= 1 only: ordinal o = position o + M (dense bases), scalar fidx[o] of the side's vector
+                        per_side = N - M;
+                        L.job[0].seg[0] = MsmSeg{fsc.p, per_side, 1, 1, 0, baseG + M, MSM_CANONICAL, fidx.p, 1};
+                        L.job[1].seg[0] = MsmSeg{fsc.p + (size_t)2 * facT * B, per_side, 1, 1, 0, baseH + M, MSM_CANONICAL, fidx.p, 1};
+                    } else if (fused) {   // the factors themselves, produced at the term fetch (no vector)
                         L.job[0].seg[0].scal = nullptr; L.job[0].seg[0].geo = 1;
                         L.job[1].seg[0].scal = nullptr; L.job[1].seg[0].geo = 2;
                         L.geo = mg;
                     }
                     L.wg_end[0] = M * L.nbk; L.wg_end[1] = 2 * M * L.nbk;
-                    launch_msm_kernel(g, L, st, stats, (uint64_t)2 * N * B, (uint64_t)2 * N * B * g->tc.windows);
+                    launch_msm_kernel(g, L, st, stats, (uint64_t)2 * per_side * B, (uint64_t)2 * per_side * B * g->tc.windows);
+                    // the unit term: one table addition per output
+                    if (unit) launch((uint64_t)2 * M * B, K_ipa_fold_unit{g->tab.p, g->tc, GHp, B, M, baseG, baseH}, st);
                 }
                 const size_t vtab_need = (size_t)VB_MULT * 4 * (M / 2 ? M / 2 : 1) * B;
                 if (!(io.vtab_pre && io.vtab_pre_count >= vtab_need)) vtab.alloc(vtab_need);
                 vsum.alloc((size_t)2 * VB_WINDOWS * B);
                 vout.alloc((size_t)2 * B);
-                linv.alloc((size_t)2 * B);
-                launch((uint64_t)2 * B, K_set_one{linv.p}, st);
+                if (!unit) {
+                    linv.alloc((size_t)2 * B);
+                    launch((uint64_t)2 * B, K_set_one{linv.p}, st);
+                }
                 vtabp = vtab.p ? vtab.p : io.vtab_pre; vsump = vsum.p; voutp = vout.p; linvp = linv.p;
             }
             const uint32_t remap = 1u;  // XCD-aware workgroup order of the window sums (vb_win_index; +1 % end to end)
@@ -259,14 +295,14 @@ static IpaEnd enqueue_ipa(const IpaIO& io, dev_stream_t st, MsmStats* stats) {
                 // multiples 1P..8P and digits of every term of this round
                 const uint32_t vcmax = handed_off ? VC_TAIL : VC;
                 const uint32_t vc = 2 * mk < vcmax ? 2 * mk : vcmax;  // chunks of the 2*mk terms of one output
-                emit((uint64_t)4 * mk * B, K_ipa_vb_tab{a, bb, GHp, linvp, vtabp, vdigp, B, mk, M}, false);
+                emit((uint64_t)4 * mk * B, K_ipa_vb_tab{a, bb, GHp, linvp, vtabp, vdigp, B, mk, M, ypos}, false);
                 emit((uint64_t)2 * VB_WINDOWS * vc * B, K_ipa_vb_win{vtabp, vdigp, vwinp, B, mk, vc, remap, 0}, true);
                 emit((uint64_t)2 * VB_WINDOWS * B, K_ge_reduce{vwinp, vsump, B, 2 * VB_WINDOWS * vc, vc}, false);  // chunk sums -> window sums
             } else {
                 // the round after: same multiples (the generators were not folded), product scalars
                 const uint32_t vcmax = handed_off ? VC_TAIL : VC;
                 const uint32_t m0 = 2 * mk, vc = 2 * m0 < vcmax ? 2 * m0 : vcmax;
-                emit((uint64_t)4 * m0 * B, K_ipa_vb_dig2{a, bb, linvp, io.uk + (size_t)(k - 1) * 2 * B, vdigp, B, m0}, false);
+                emit((uint64_t)4 * m0 * B, K_ipa_vb_dig2{a, bb, linvp, io.uk + (size_t)(k - 1) * 2 * B, vdigp, B, m0, ypos}, false);
                 emit((uint64_t)2 * VB_WINDOWS * vc * B, K_ipa_vb_win{vtabp, vdigp, vwinp, B, m0, vc, remap, 1}, true);
                 emit((uint64_t)2 * VB_WINDOWS * B, K_ge_reduce{vwinp, vsump, B, 2 * VB_WINDOWS * vc, vc}, false);
             }
@@ -281,7 +317,7 @@ static IpaEnd enqueue_ipa(const IpaIO& io, dev_stream_t st, MsmStats* stats) {
         else if (!vb_reuse) {
             vb_reuse = k + 1 < lgN;  // the next round works on this round's multiples
         } else {
-            if (k + 1 < lgN) emit((uint64_t)2 * mk * B, K_ipa_vb_fold2{GHp, io.uk + (size_t)(k - 1) * 2 * B, ukk, linvp, vtabp, B, 2 * mk, M}, false);
+            if (k + 1 < lgN) emit((uint64_t)2 * mk * B, K_ipa_vb_fold2{GHp, io.uk + (size_t)(k - 1) * 2 * B, ukk, linvp, vtabp, B, 2 * mk, M, ypos}, false);
             vb_reuse = false;
         }
     }

@@ -1274,11 +1274,68 @@ struct K_ipa_fold_from_tables {  // gid = (side*M + j)*B + b
         GH[g] = ge_from_table_class(acc);
     }
 };
+// The unit form of that launch (enqueue_ipa, jobs of the shipped MSM kernel with closed-form factors).  The 2^r coefficients of a
+// side are the subset products of r challenges, so divided by the coefficient c_0 of block 0 exactly one of them is 1:
+//   G^(r)_j = c_0 * Gs_j,          Gs_j = G_j + sum_{t>=1} (c_t / c_0) e_{j+tM} G_{j+tM}
+//   H^(r)_j = c_0 * y^-j * Hs_j,   Hs_j = H_j + sum_{t>=1} (c_t / c_0) y^-(tM) e_{j+tM} H_{j+tM}
+// (e: the padding factor from n1 >= M on).  The launch sums the 2^r - 1 terms t >= 1, whose scalars no longer depend on j beyond the
+// padding flag; the unit term is ONE table addition per output (K_ipa_fold_unit) instead of a term's 23; c_0 goes into linv and
+// y^-j into the scalars of the rounds that follow (YPos).
+struct K_ipa_fold_scal {  // gid = (side*T + t)*B + b : out[side][t][e][b] = (c_t / c_0) [* y^-(tM)] [* padding factor], canonical
+    const sc* fac;   // K_ipa_fac's arrays as of round r
+    const sc* uk;    // [r][2][B] u_k, u_k^-1 of the rounds before
+    const sc* lo1;   // y^-1 power tables (low: 256 entries, high)
+    const sc* hi1;
+    sc* out;         // [2][T][2][B]
+    sc* linv;        // [2][B] Montgomery: c_0 of either side
+    uint32_t B, T, r, M;
+    HD void operator()(uint32_t g) const {
+        const uint32_t b = g % B, st = g / B, side = st / T, t = st % T;
+        // 1 / c_0 without an inversion: c_0 = prod u_k^-1 (G: the lower half of a block takes u^-1), prod u_k (H)
+        sc inv0 = sc_one_mont();
+        for (uint32_t k = 0; k < r; k++) inv0 = sc_mul(inv0, uk[((size_t)k * 2 + side) * B + b]);
+        if (side) {
+            const uint32_t p = t * M;
+            inv0 = sc_mul(inv0, sc_mul(lo1[(size_t)(p & 255u) * B + b], hi1[(size_t)(p >> 8) * B + b]));
+        }
+        for (uint32_t e = 0; e < 2; e++)   // (Montgomery form times canonical integer = canonical product)
+            out[(((size_t)side * T + t) * 2 + e) * B + b] = sc_mul(inv0, fac[((size_t)(2 + 2 * side + e) * T + t) * B + b]);
+        if (t == 0) linv[(size_t)side * B + b] = fac[(size_t)side * T * B + b];   // entry 0 of the Montgomery chain = block 0
+    }
+};
+struct K_ipa_fold_idx {  // gid = o < N - M : which of a side's 2 T scalars the term at position o + M takes
+    uint32_t* sidx;
+    uint32_t M, n1;
+    HD void operator()(uint32_t o) const {
+        const uint32_t i = o + M;
+        sidx[o] = 2u * (i / M) + (i >= n1 ? 1u : 0u);
+    }
+};
+struct K_ipa_fold_unit {  // gid = (side*M + j)*B + b : GH += G_j / H_j, slot 1 of window 0 of the base's row
+    const uint8_t* tab;
+    TabCfg tc;
+    ge* GH;  // [2][M][B]
+    uint32_t B, M, baseG, baseH;
+    HD void operator()(uint32_t g) const {
+        const uint32_t sj = g / B, side = sj / M, j = sj % M;
+        const uint8_t* row = tab + (size_t)((side ? baseH : baseG) + j) * tc.base_bytes();
+        GH[g] = ge_from_table_class(ge_madd_t(GH[g], ge_niels_load(row + tc.stride), 0));
+    }
+};
 // Variable-base part of the IPA (rounds >= r).  The stored per-proof generators are SCALED:
 //   Ghat = lamG * G_true,  Hhat = lamH * H_true   (lamG = prod u_k, lamH = prod u_k^-1 over the folded rounds)
 // so that a fold needs ONE scalar multiplication per output, Ghat' = Ghat_lo + u^2 * Ghat_hi,
 // instead of upstream's two (u^-1*G_lo + u*G_hi); the scale is divided out of the L/R scalars
 // (linv = lam^-1).  Group elements are exact, so L_k / R_k are bit-identical.
+// With the unit form of the first fold (above) linv starts at c_0 instead of 1 and the H side carries a POSITION factor on top:
+//   H_true[j] = linvH * y^-j * Hhat[j]   at every level (j: position in the level's vector).
+// The factor stays geometric in j through a fold - u H_true[j] + u^-1 H_true[j+m] = (linvH u) y^-j (Hhat[j] + u^-2 y^-m Hhat[j+m]) -
+// so every H-side scalar takes y^-p, p the position of the point it multiplies, and the scale linv moves as before.
+struct YPos {   // the y^-1 power tables (K_pow_tables: low 256 entries, high), or null: no position factor
+    const sc* lo = nullptr;
+    const sc* hi = nullptr;
+    HD sc at(uint32_t p, uint32_t B, uint32_t b) const { return sc_mul(lo[(size_t)(p & 255u) * B + b], hi[(size_t)(p >> 8) * B + b]); }
+};
 // L_k / R_k of a variable-base round are multiscalar multiplications over 2m per-proof points each.  Straus with the
 // doublings SHARED by all terms: (1) per term, the multiples 1P..16P and the 51 signed radix-32 digits of its scalar;
 // (2) per (output, window, chunk of terms) the sum of the selected multiples - no doublings at all; (3) per output
@@ -1332,13 +1389,16 @@ struct K_ipa_vb_tab {  // gid = (w*m + j)*B + b, w<4 (0 = a_lo*G_hi, 1 = b_hi*H_
     ge_cached* vtab;    // [VB_MULT][4*m*B] multiples 1P..16P
     uint32_t* vdig;     // [VB_WORDS][4*m*B] packed signed digits, least significant first
     uint32_t B, m, M;
+    YPos ypos;          // H side: the scalar takes y^-(position of its point) on top
     HD void operator()(uint32_t g) const {
         uint32_t b = g % B, wj = g / B, w = wj / m, j = wj % m;
         uint32_t side = w & 1u;  // branch-free operand selection
         const sc* sv = side ? bb : a;
         const ge* pv = side ? GH + (size_t)M * B : GH;
         uint32_t s_hi = (w == 1u) | (w == 2u), p_hi = (w == 0u) | (w == 3u);
-        sc s = sc_from_mont(sc_mul(sv[(size_t)(j + s_hi * m) * B + b], linv[(size_t)side * B + b]));
+        sc sm = sc_mul(sv[(size_t)(j + s_hi * m) * B + b], linv[(size_t)side * B + b]);
+        if (side && ypos.lo) sm = sc_mul(sm, ypos.at(j + p_hi * m, B, b));
+        sc s = sc_from_mont(sm);
         ge P = pv[(size_t)(j + p_hi * m) * B + b];
         size_t stride = (size_t)4 * m * B;
         ge_cached c1 = ge_to_cached(P);
@@ -1442,6 +1502,7 @@ struct K_ipa_vb_dig2 {  // gid = (w*m + j)*B + b over round k's layout (w: 0 G_h
     const sc* uk;     // [2][B] u_k, u_k^-1
     uint32_t* vdig;   // [VB_WORDS][4*m*B]
     uint32_t B, m;
+    YPos ypos;        // H side: y^-(position of the point in round k's vector) on top (the y^-m of a "hi" point's weight included)
     HD void operator()(uint32_t g) const {
         uint32_t b = g % B, wj = g / B, w = wj / m, j = wj % m, h = m >> 1;
         uint32_t side = w & 1u, hi = (w == 0u) | (w == 3u);
@@ -1450,6 +1511,7 @@ struct K_ipa_vb_dig2 {  // gid = (w*m + j)*B + b over round k's layout (w: 0 G_h
         uint32_t idx = j >= h ? j - h : j + h;
         // scale of the level-(k+1) generators: linv' = linv * f^-1 (G: f = u, H: f = u^-1); "hi" points carry f^2 on top
         sc fac = sc_mul(linv[(size_t)side * B + b], uk[(size_t)((side ^ hi) ? 0u : 1u) * B + b]);
+        if (side && ypos.lo) fac = sc_mul(fac, ypos.at(j + hi * m, B, b));
         sc s = sc_from_mont(sc_mul(sv[(size_t)idx * B + b], fac));
         uint32_t dig[VB_WORDS];
         vb_recode(s, dig);
@@ -1472,6 +1534,7 @@ struct K_ipa_vb_fold2 {  // gid = (side*h + j)*B + b : Ghat''[j] = Ghat[j] + w0 
     sc* linv;       // [2][B]
     const ge_cached* vtab;  // [VB_MULT][4*m*B]
     uint32_t B, m, M;
+    YPos ypos;      // H side: the weight of a point takes y^-(its position offset: m, h, m + h) on top
     HD void operator()(uint32_t g) const {
         // lanes of a wavefront = consecutive proofs (coalesced reads of the multiples); signs are applied without branching
         const uint32_t h = m >> 1;
@@ -1480,6 +1543,7 @@ struct K_ipa_vb_fold2 {  // gid = (side*h + j)*B + b : Ghat''[j] = Ghat[j] + w0 
         const uint32_t fi = side ? 1u : 0u;  // G: f = u ; H: f = u^-1
         sc f0 = uk0[(size_t)fi * B + b], f1 = uk1[(size_t)fi * B + b];
         sc w0m = sc_mul(f0, f0), w1m = sc_mul(f1, f1);
+        if (side && ypos.lo) { w0m = sc_mul(w0m, ypos.at(m, B, b)); w1m = sc_mul(w1m, ypos.at(h, B, b)); }
         uint32_t p0[VB_WORDS], p1[VB_WORDS], p01[VB_WORDS];
         vb_recode(sc_from_mont(w0m), p0);
         vb_recode(sc_from_mont(w1m), p1);
@@ -1510,7 +1574,7 @@ struct K_ipa_vb_fold2 {  // gid = (side*h + j)*B + b : Ghat''[j] = Ghat[j] + w0 
         }
     }
 };
-struct K_set_one {  // linv = 1
+struct K_set_one {  // linv = 1 (all 2^r terms from the tables; the unit form's scales: K_ipa_fold_scal)
     sc* p;
     HD void operator()(uint32_t g) const { p[g] = sc_one_mont(); }
 };
