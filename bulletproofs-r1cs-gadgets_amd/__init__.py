@@ -65,18 +65,23 @@ OPT_SECRET_INDEPENDENT = 11   # creation only: the commit phase through k_msm_fi
 OPT_VERIFY_GROUP, OPT_VERIFY_GROUP_FALLBACK = 12, 13   # verify_batch: one combined check per group of proofs, re-check of a failing group
 # values of OPT_VERIFY_GROUP_FALLBACK: a failing group's proofs all get verdict 0 / are re-checked one by one / are bisected on the device
 VERIFY_GROUP_FALLBACK_NONE, VERIFY_GROUP_FALLBACK_RECHECK, VERIFY_GROUP_FALLBACK_BISECT = 0, 1, 2
+OPT_CHECK_WITNESS = 14   # prove calls: check every assignment on the device and refuse the proofs that violate the circuit (refusal())
+PROOF_REFUSED = 0xFF     # byte 0 of a refusal record; the offsets of its little-endian words (include/bpr1cs.h BPR1CS_REFUSAL_OFF_*)
+REFUSAL_OFF_GATE, REFUSAL_OFF_ROW, REFUSAL_OFF_GATE_COUNT, REFUSAL_OFF_ROW_COUNT = 4, 8, 12, 16
 OPTIONS = dict(unfold=OPT_UNFOLD_ROUNDS, witness_team=OPT_WITNESS_TEAM, tail_rounds=OPT_TAIL_ROUNDS, shared_back=OPT_SHARED_BACK,
                factor_vectors=OPT_FACTOR_VECTORS, msm_threads_log2=OPT_MSM_THREADS_LOG2, job_proofs=OPT_JOB_PROOFS,
                jobs_in_flight=OPT_JOBS_IN_FLIGHT, host_chain_proofs=OPT_HOST_CHAIN_PROOFS, window_bits=OPT_WINDOW_BITS,
                host_chain_share=OPT_HOST_CHAIN_SHARE, secret_independent=OPT_SECRET_INDEPENDENT,
-               verify_group=OPT_VERIFY_GROUP, verify_group_fallback=OPT_VERIFY_GROUP_FALLBACK)
+               verify_group=OPT_VERIFY_GROUP, verify_group_fallback=OPT_VERIFY_GROUP_FALLBACK,
+               check_witness=OPT_CHECK_WITNESS)
 
 
 class ProveStats(ctypes.Structure):
     """bpr1cs_prove_stats (include/bpr1cs.h)"""
     _fields_ = [("jobs", ctypes.c_uint32), ("job_proofs", ctypes.c_uint32), ("phase_ms", ctypes.c_float * 6), ("msm_ms", ctypes.c_double),
                 ("msm_launches", ctypes.c_uint64), ("msm_terms", ctypes.c_uint64), ("msm_adds", ctypes.c_uint64), ("host_chains", ctypes.c_uint64),
-                ("sizing_free_bytes", ctypes.c_uint64), ("sizing_bytes_per_proof", ctypes.c_uint64), ("sizing_fixed_bytes", ctypes.c_uint64)]
+                ("sizing_free_bytes", ctypes.c_uint64), ("sizing_bytes_per_proof", ctypes.c_uint64), ("sizing_fixed_bytes", ctypes.c_uint64),
+                ("refused", ctypes.c_uint64)]
 
 
 def load_library(path=None):
@@ -275,6 +280,16 @@ def prove_batch(gens, circuit, label, values, v_blindings, rng_seeds, batch, wir
     P = [praw[i * plen:(i + 1) * plen] for i in range(batch)]
     C = [[craw[(i * m + j) * 32:(i * m + j + 1) * 32] for j in range(m)] for i in range(batch)]
     return P, C
+
+
+def refusal(proof_bytes):
+    """A slot of a prove call's output under OPT_CHECK_WITNESS: None for a proof, for a refusal record (include/bpr1cs.h) the dict
+    gate / row (lowest violated multiplier / constraint, None: none) and gates / rows (how many are violated)."""
+    if len(proof_bytes) < 20 or proof_bytes[0] != PROOF_REFUSED:
+        return None
+    w = lambda off: int.from_bytes(proof_bytes[off:off + 4], "little")
+    first = lambda off: None if w(off) == 0xFFFFFFFF else w(off)
+    return dict(gate=first(REFUSAL_OFF_GATE), row=first(REFUSAL_OFF_ROW), gates=w(REFUSAL_OFF_GATE_COUNT), rows=w(REFUSAL_OFF_ROW_COUNT))
 
 
 def verify_batch(gens, circuit, label, proofs, commitments, batch, seeds=None):
@@ -525,7 +540,8 @@ def last_prove_stats(lib=None):
     st = ProveStats()
     _chk(lib.bpr1cs_last_prove_stats(ctypes.byref(st)))
     return dict(jobs=st.jobs, job_proofs=st.job_proofs, phase_ms=list(st.phase_ms), msm_ms=st.msm_ms, msm_launches=st.msm_launches, msm_terms=st.msm_terms, msm_adds=st.msm_adds, host_chains=st.host_chains,
-                sizing_free_bytes=st.sizing_free_bytes, sizing_bytes_per_proof=st.sizing_bytes_per_proof, sizing_fixed_bytes=st.sizing_fixed_bytes)
+                sizing_free_bytes=st.sizing_free_bytes, sizing_bytes_per_proof=st.sizing_bytes_per_proof, sizing_fixed_bytes=st.sizing_fixed_bytes,
+                refused=st.refused)
 
 
 def prove_batch_transcripts(gens, circuit, transcripts, values, v_blindings, rng_seeds, batch, wires=None):

@@ -54,6 +54,7 @@ struct BpOpts {
     std::atomic<int> host_chain_share{-1}; // percent of a larger job's chains streamed from host threads (-1: 100 for a job that follows another of its call, with AVX-512)
     std::atomic<int> verify_group{0};      // proofs per group of bpr1cs_verify_batch's grouped form (0, 1: off - one mega-check per proof)
     std::atomic<int> verify_group_fallback{1};  // 1: the proofs of a failing group are re-checked one by one, 0: they all get verdict 0, 2: the culprits are found by bisection on the device
+    std::atomic<int> check_witness{0};     // 1: every prove job checks its assignment on the device and refuses the proofs that violate the circuit
     int window_bits = 0;                   // creation only (0: from the free memory)
     int secret_independent = 0;            // creation only: 1 = the commit phase runs through k_msm_fixed_ct over a narrow table set of its own
 };
@@ -72,6 +73,7 @@ static bool opt_apply(BpOpts& o, int option, int value, bool creating) {
         case BPR1CS_OPT_HOST_CHAIN_SHARE: o.host_chain_share = value < 0 ? -1 : (value > 100 ? 100 : value); return true;
         case BPR1CS_OPT_VERIFY_GROUP: o.verify_group = value < 0 ? 0 : (value > 4096 ? 4096 : value); return true;
         case BPR1CS_OPT_VERIFY_GROUP_FALLBACK: o.verify_group_fallback = value < 0 ? 1 : (value == BPR1CS_VERIFY_GROUP_FALLBACK_BISECT ? 2 : (value ? 1 : 0)); return true;
+        case BPR1CS_OPT_CHECK_WITNESS: o.check_witness = value <= 0 ? 0 : 1; return true;
         case BPR1CS_OPT_WINDOW_BITS:
             if (!creating) return false;
             o.window_bits = value <= 0 ? 0 : (value < 4 ? 4 : (value > 15 ? 15 : value));   // (digits travel as sign + 15-bit magnitude: |d| <= 2^14 at W = 15)
@@ -173,6 +175,7 @@ struct bpr1cs_gens {
     // per draw: dead after its reduction mod l).  The next job's writers wait for the event the previous job records when it is done
     // with them - long before, in steady state: a job's front starts when its predecessor's back phase does.
     mutable DevArena shared_front;
+    mutable DevBuf<uint32_t> check_res[2];   // BPR1CS_OPT_CHECK_WITNESS: the result block of the slot's job (16 B per proof), grown on demand
     mutable dev_event_t w_free_ev{}, rng_free_ev{};
     mutable std::atomic<uint32_t> busy_slots{0};  // bit s: job slot s (streams jstream[s], arena front[s]) belongs to a job in flight
     mutable std::atomic<int> in_flight{0};  // jobs begun and not yet ended
@@ -218,6 +221,16 @@ struct bpr1cs_circuit {
     };
     mutable std::mutex mt_mu;
     mutable std::map<const bpr1cs_gens*, MergedTab*> mt;
+    // BPR1CS_OPT_CHECK_WITNESS: the constraints BY ROW (the arrays above hold them by wire slot), built by bpr1cs_circuit_create on the
+    // host and uploaded under mt_mu by the first checked job of the circuit - a circuit that is never checked holds none of it on the
+    // device.  Per entry a slot word (the flattening's numbering, bits 31 / 30 = coefficient +1 / -1 as in ent_row) and a Montgomery
+    // coefficient; chunks of consecutive WHOLE rows (row_chunk[k] = first row of chunk k, closed at CHECK_CHUNK entries).
+    std::vector<uint32_t> h_row_off, h_row_slot, h_row_chunk;
+    std::vector<sc> h_row_coeff;
+    mutable DevBuf<uint32_t> row_off, row_slot, row_chunk;
+    mutable DevBuf<sc> row_coeff;
+    mutable bool rows_uploaded = false;
+    size_t row_form_bytes() const { return h_row_slot.size() * 36 + (h_row_off.size() + h_row_chunk.size()) * 4; }
     // circuit cache (below): the description this object was built from, and how many handles the callers hold on it
     int cache_refs = -1;   // -1: not in the cache (bpr1cs_circuit_destroy deletes it)
     int cache_device = 0;  // the device its buffers live on

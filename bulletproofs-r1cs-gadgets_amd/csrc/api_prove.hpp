@@ -13,6 +13,7 @@ struct bpr1cs_job {
     uint8_t* h_proofs = nullptr;  // pinned staging
     uint8_t* h_comms = nullptr;
     int* h_err = nullptr;
+    uint32_t* h_chk = nullptr;    // BPR1CS_OPT_CHECK_WITNESS: the job's result block, 4 words per proof (K_check_init), else null
     strobe* h_tr = nullptr;       // final transcript states (only when the caller handed in its own transcripts)
     bool counted = false;         // contributes to g->in_flight
     int slot = -1;                // the handle's job slot it holds (released with the job)
@@ -117,6 +118,7 @@ static void job_release(bpr1cs_job* job) {
     host_stage_free(job->h_proofs);
     host_stage_free(job->h_comms);
     host_stage_free(job->h_err);
+    host_stage_free(job->h_chk);
     host_stage_free(job->h_tr);
     if (job->counted) job->g->in_flight--;
     if (job->slot >= 0) job->g->busy_slots.fetch_and(~(1u << job->slot));
@@ -154,6 +156,32 @@ static int prove_job_fail(const bpr1cs_gens* g, bpr1cs_job* job, uint32_t slot, 
     } catch (...) {}
     job_release(job);
     return code;
+}
+
+// BPR1CS_OPT_CHECK_WITNESS: the job's assignment - wires W, committed values v_m - against the circuit, enqueued on the
+// stream that produced W, directly behind the producer and in front of the event the commit sums wait for (ev_wit).  That event is
+// also what keeps the NEXT job in flight away: it overwrites the shared W only after g->w_free_ev, which this job records on the
+// heavy stream behind l(x), r(x) - and the heavy stream has waited for ev_wit.  The circuit's row form goes to the device here, once,
+// under the circuit's mutex (as its merged tables do): synchronous copies, so a later job on any stream finds it complete.
+static void enqueue_witness_check(const bpr1cs_circuit* c, const sc* W, const sc* v_m, uint32_t* res, uint32_t B, dev_stream_t s) {
+    {
+        std::lock_guard<std::mutex> lk(c->mt_mu);
+        if (!c->rows_uploaded) {
+            ArenaScope persistent(nullptr);   // the row form outlives the job
+            upload(c->row_off, c->h_row_off, s);
+            upload(c->row_slot, c->h_row_slot, s);
+            upload(c->row_coeff, c->h_row_coeff, s);
+            upload(c->row_chunk, c->h_row_chunk, s);
+            c->rows_uploaded = true;
+        }
+    }
+    const uint32_t Bpad = (B + 63u) & ~63u;
+    launch(B, K_check_init{res}, s);
+    launch((uint64_t)((c->n + CHECK_GATES - 1) / CHECK_GATES) * Bpad, K_check_gates{W, res, B, Bpad, c->n}, s);
+    const uint32_t nchunks = (uint32_t)c->h_row_chunk.size() - 1, per_launch = 0xffffffffu / Bpad;   // (a grid holds 2^32 - 1 threads)
+    for (uint32_t c0 = 0; c0 < nchunks; c0 += per_launch)
+        launch((uint64_t)std::min(per_launch, nchunks - c0) * Bpad,
+               K_check_rows{c->row_chunk.p, c->row_off.p, c->row_slot.p, c->row_coeff.p, W, v_m, res, B, Bpad, 3 * c->n, c->m, c0}, s);
 }
 
 // One device job.  `init`: the transcripts the proofs start from - n_init = 1 (every proof starts from a copy of init[0]: what
@@ -204,6 +232,7 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     ArenaScope own_arena(&g->front[slot], true);
     // the handle's options, read once per job
     const int o_team = g->opts.witness_team.load(), o_tail = g->opts.tail_rounds.load();
+    const bool o_check = g->opts.check_witness.load() != 0;
     const uint32_t B = (uint32_t)batch, n = c->n, m = c->m, N = c->N, lgN = c->lgN;
     const int o_unfold = (int)eff_unfold(g->opts, B, lgN);
     const uint32_t baseG = 2, baseH = 2 + g->cap;
@@ -366,6 +395,15 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
 
     // ---- P7/P8: witness (device program) or host-synthesised wires (in a small job: while the host threads hash)
     DevBuf<sc> px;
+    // the witness check's result block belongs to the job SLOT, like the slot's arena (the slot's previous job has ended), so two jobs
+    // in flight never share it - but it is not one of the arena's blocks: the arena hands them out in request order, and one more
+    // request in the middle would make every later block of a job miss its slot whenever the option changes between two calls
+    struct { uint32_t* p; } chk{nullptr};
+    if (o_check) {
+        DevBuf<uint32_t>& blk = g->check_res[slot];
+        if (blk.n < (size_t)4 * B) { ArenaScope persistent(nullptr); blk.alloc((size_t)4 * B); }
+        chk.p = blk.p;
+    }
     if (wires) {
         // Host wires go in on the job's witness stream, as the device program's do: the A_I1 / A_O1 sums need nothing else, so they -
         // and the host's enqueuing of the whole back phase - do not wait for the TranscriptRng chain: the heavy stream waits for the
@@ -377,6 +415,10 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
         if (shared) dev_stream_wait(sw, g->w_free_ev);
         launch((uint64_t)3 * n * B, K_load_wires_pm{raw.p, W.p, B, 3 * n}, sw);
         dev_zero(raw.p, raw.bytes(), sw);
+        if (o_check) {
+            dev_stream_wait(sw, job->ev_in);   // the committed values in Montgomery form (K_load_inputs, front stream)
+            enqueue_witness_check(c, W.p, v_m.p, chk.p, B, sw);
+        }
         dev_event_create(&job->ev_wit);
         dev_event_record(job->ev_wit, sw);
         dev_stream_wait(st, job->ev_wit);
@@ -392,6 +434,7 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
 #if defined(BPR1CS_HOSTSIM)
         (void)o_team;
         launch(B, kw, st);
+        if (o_check) enqueue_witness_check(c, W.p, v_m.p, chk.p, B, st);
 #else
         int T = o_team;
         if (c->n_perms && (uint32_t)T < c->macro_width + 2) T = 16;  // poseidon_team needs width + 2 lanes
@@ -403,6 +446,7 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
         else if (T == 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_witness_team<8>), dim3(blocks), dim3(64), 0, job->st3, kw);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_witness_team<16>), dim3(blocks), dim3(64), 0, job->st3, kw);
         HIPCHK(hipGetLastError());
+        if (o_check) enqueue_witness_check(c, W.p, v_m.p, chk.p, B, job->st3);
         dev_event_create(&job->ev_wit);
         dev_event_record(job->ev_wit, job->st3);
         dev_stream_wait(st, job->ev_wit);
@@ -702,6 +746,10 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
         launch_wipe(kw, st);
     }
     dev_d2h_async(job->h_err, rng_err.p, sizeof(int), st);
+    if (o_check) {
+        job->h_chk = (uint32_t*)host_stage_alloc((size_t)B * 16);
+        dev_d2h_async(job->h_chk, chk.p, (size_t)B * 16, st);
+    }
     dev_event_create(&job->ev_done);
     dev_event_record(job->ev_done, st);
     g->in_flight++;
@@ -732,6 +780,22 @@ static int prove_job_end(bpr1cs_job* job, uint8_t* proofs_out, uint8_t* commitme
         if (tr_out && job->h_tr)
             for (uint32_t b = 0; b < job->B; b++) tr_out[b]->s = job->h_tr[b];
         if (*job->h_err) rc = BPR1CS_ERR_INVALID_ARGUMENT;  // RNG stream kernel found a non-steady STROBE state
+        // BPR1CS_OPT_CHECK_WITNESS: a proof whose assignment failed a check leaves as a refusal record (include/bpr1cs.h) - written here,
+        // on the host, over bytes the job computed like every other proof's
+        uint32_t refused = 0;
+        if (job->h_chk)
+            for (uint32_t b = 0; b < job->B; b++) {
+                const uint32_t* r = job->h_chk + 4 * (size_t)b;
+                if (r[0] == 0xffffffffu && r[1] == 0xffffffffu && !r[2] && !r[3]) continue;
+                uint8_t* p = proofs_out + (size_t)b * job->plen;
+                memset(p, 0, job->plen);
+                p[0] = BPR1CS_PROOF_REFUSED;
+                const uint32_t w[4] = {r[0], r[1], r[2], r[3]};   // first gate, first row, gates, rows
+                const size_t off[4] = {BPR1CS_REFUSAL_OFF_GATE, BPR1CS_REFUSAL_OFF_ROW, BPR1CS_REFUSAL_OFF_GATE_COUNT, BPR1CS_REFUSAL_OFF_ROW_COUNT};
+                for (int k = 0; k < 4; k++)
+                    for (int i = 0; i < 4; i++) p[off[k] + i] = (uint8_t)(w[k] >> (8 * i));
+                refused++;
+            }
         float ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         try {
             job->pt.finish(ph);
@@ -744,6 +808,7 @@ static int prove_job_end(bpr1cs_job* job, uint8_t* proofs_out, uint8_t* commitme
             acc->msm_ms += job->msm.ms; acc->msm_launches += job->msm.launches; acc->msm_terms += job->msm.terms; acc->msm_adds += job->msm.adds;
             if (job->host_chain) acc->host_chains += job->B;
             else acc->host_chains += job->Bh;
+            acc->refused += refused;
         }
     }
     job_release(job);
@@ -768,11 +833,16 @@ static uint32_t auto_job_proofs(const bpr1cs_gens* g, const bpr1cs_circuit* c, b
                          tail_m * (2 * 32 + 2 * sizeof(ge)) + (tail_m / 2) * (4 * VB_MULT * sizeof(ge_cached) + 4 * VB_WORDS * 4) + 2 * VB_WINDOWS * 5 * sizeof(ge);
     const size_t others = 32 * (3 * n + m + nfl) + 64 * N, vt = r < c->lgN ? (size_t)VB_MULT * 4 * std::max<size_t>(1, Mr / 2) * sizeof(ge_cached) : 0;
     const size_t back = std::max(others, vt) + 64 * N + 2 * VB_WINDOWS * sizeof(ge) + 30000;   // (folded generators, digits, window sums: inside the dead rows of l / r)
+    const bool check = g->opts.check_witness.load() != 0;
     size_t fixed = (size_t)5 << 29;   // chunk partial sums of the MSM launches (~2^21 points each, whatever the batch: six buffers in the shared arena), staging
     if (have_program && !c->h_trip.empty() && !g->ct()) {   // (a secret-independent handle takes the plain sums: no merged tables)
         std::lock_guard<std::mutex> lk(c->mt_mu);
         auto it = c->mt.find(g);
         if (it == c->mt.end() || !it->second->tab.p) fixed += 2 * c->h_trip.size() * merged_tab_cfg(g, (uint32_t)c->h_trip.size()).base_bytes();
+    }
+    if (check) {   // the circuit's row form, while the first checked job has still to upload it (16 B of result per proof are within `front`'s slack)
+        std::lock_guard<std::mutex> lk(c->mt_mu);
+        if (!c->rows_uploaded) fixed += c->row_form_bytes();
     }
     const size_t avail = dev_free_memory() + g->arena.bytes() + g->front[0].bytes() + g->front[1].bytes() + g->shared_front.bytes();
     const size_t reserve = (size_t)4 << 30;   // what must stay free at the peak (the HIP runtime's own needs, another handle's small jobs)

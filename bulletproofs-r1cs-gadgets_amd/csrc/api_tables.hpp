@@ -41,6 +41,8 @@ int bpr1cs_gens_release_scratch(bpr1cs_gens* g) {
     g->front[0].release();
     g->front[1].release();
     g->shared_front.release();
+    for (auto& blk : g->check_res)
+        if (blk.p) { dev_free_now(blk.p); blk.p = nullptr; blk.n = 0; }
     g->sizing_epoch++;
     return BPR1CS_OK;
 }
@@ -281,6 +283,31 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
         upload(c->slot_chunk, sch, s);
     }
     upload(c->ent_coeff, ent_coeff, s);
+    {   // the same constraints by row, for K_check_rows (BPR1CS_OPT_CHECK_WITNESS): host copy only, uploaded by the first checked job
+        c->h_row_off.assign(1, 0);
+        if (d->q) c->h_row_off.assign(d->row_off, d->row_off + d->q + 1);
+        c->h_row_slot.resize(nnz);
+        c->h_row_coeff.resize(nnz);
+        for (uint32_t t = 0; t < nnz; t++) {
+            uint32_t slot = 0;
+            (void)slot_of(d->term_var[t], slot);   // (validated by the counting loop above)
+            const sc co = host_mont(d->term_coeff + 32 * (size_t)t);
+            c->h_row_coeff[t] = co;
+            // (slot <= 3n + m < 2^26: the two top bits carry the +-1 flags, as in ent_row)
+            c->h_row_slot[t] = slot | (memcmp(&co, &one_m, sizeof(sc)) == 0 ? 0x80000000u : 0u) | (memcmp(&co, &minus_one_m, sizeof(sc)) == 0 ? 0x40000000u : 0u);
+        }
+        // chunks of consecutive whole rows, closed when their entries reach CHECK_CHUNK: a row is never split, a row of CHECK_CHUNK
+        // entries or more is a chunk of its own, empty rows ride along
+        uint32_t start = 0, cnt_e = 0;
+        for (uint32_t j = 0; j < d->q; j++) {
+            const uint32_t len = d->row_off[j + 1] - d->row_off[j];
+            if (len >= CHECK_CHUNK && j > start) { c->h_row_chunk.push_back(start); start = j; cnt_e = 0; }
+            cnt_e += len;
+            if (cnt_e >= CHECK_CHUNK) { c->h_row_chunk.push_back(start); start = j + 1; cnt_e = 0; }
+        }
+        if (start < d->q) c->h_row_chunk.push_back(start);
+        c->h_row_chunk.push_back(d->q);   // [nchunks + 1]
+    }
     if (d->wops) {
         c->has_program = true;
         std::vector<WOp> ops(d->n);

@@ -890,6 +890,88 @@ struct K_flatten {  // gid = s*B + b
     }
 };
 
+// ------------------------------------------------------ witness check (BPR1CS_OPT_CHECK_WITNESS)
+// Is the assignment a job is about to prove a solution of its circuit?  a_L[i] a_R[i] = a_O[i] for every multiplier, and
+// sum coeff * value = 0 for every constraint (value(One) = 1; wires and committed values as they were handed in).  Result block:
+// 4 words per proof - lowest violated multiplier, lowest violated row (~0: none), the two counts (a count is at most n <= 2^24 /
+// q <= 2^26: it cannot wrap) - set to {~0, ~0, 0, 0} by K_check_init.  A thread walks its gates / rows, and only one that FOUND a
+// violation touches the block (one atomic minimum, one atomic addition): a job of good witnesses executes no atomic at all, and a
+// minimum and a sum do not depend on the order of the threads.  Addresses and grids are functions of the circuit and the batch size.
+#define CHECK_CHUNK 256u   // entries per chunk of whole rows (api_tables.hpp builds the chunk list)
+#define CHECK_GATES 16u    // multipliers per thread of K_check_gates
+HD inline void check_report(uint32_t* res, uint32_t first, uint32_t count) {   // res: the first-index word, its count two words on
+#if defined(__HIP_DEVICE_COMPILE__)
+    atomicMin(res, first);
+    atomicAdd(res + 2, count);
+#else
+    if (first < res[0]) res[0] = first;
+    res[2] += count;
+#endif
+}
+struct K_check_init {  // gid = b
+    uint32_t* res;  // [B][4]
+    HD void operator()(uint32_t b) const {
+        res[4 * (size_t)b + 0] = 0xffffffffu; res[4 * (size_t)b + 1] = 0xffffffffu;
+        res[4 * (size_t)b + 2] = 0; res[4 * (size_t)b + 3] = 0;
+    }
+};
+// gid = c * Bpad + b, Bpad = B rounded up to 64: the proof index is minor and a wavefront never straddles two chunks, so the multiplier
+// index is the same for its 64 lanes and the three 32-byte loads are consecutive across them
+struct K_check_gates {
+    const sc* W;    // [3][n][B] a_L a_R a_O, Montgomery
+    uint32_t* res;
+    uint32_t B, Bpad, n;
+    HD void operator()(uint32_t g) const {
+        const uint32_t c = g / Bpad, b = g % Bpad;
+        if (b >= B) return;
+        const uint32_t lo = c * CHECK_GATES, hi = lo + CHECK_GATES < n ? lo + CHECK_GATES : n;
+        const size_t nb = (size_t)n * B;
+        uint32_t first = 0xffffffffu, count = 0;
+        for (uint32_t i = lo; i < hi; i++) {
+            const size_t ib = (size_t)i * B + b;
+            if (!sc_is_zero(sc_sub(sc_mul(W[ib], W[nb + ib]), W[2 * nb + ib]))) {
+                if (!count) first = i;
+                count++;
+            }
+        }
+        if (count) check_report(res + 4 * (size_t)b, first, count);
+    }
+};
+// gid = (c - c0) * Bpad + b: thread (chunk c of whole rows, proof b).  Row offsets, slot words and coefficients are same-address reads
+// across a wavefront (one chunk), the value loads X[slot][b] are consecutive across its lanes - the pattern of K_flatten_chunks, whose
+// +-1 flags (no multiplication for most coefficients of the reference's gadgets) the slot words carry too.  X = W followed by the
+// committed values followed by the constant: two base pointers, selected by the slot.
+struct K_check_rows {
+    const uint32_t* row_chunk;  // [nchunks + 1] first row of every chunk
+    const uint32_t* row_off;    // [q + 1]
+    const uint32_t* row_slot;   // bit 31 / bit 30: the coefficient is +1 / -1
+    const sc* row_coeff;        // Montgomery
+    const sc* W;                // [3n][B]
+    const sc* v_m;              // [m][B]
+    uint32_t* res;
+    uint32_t B, Bpad, n3, m, c0;
+    HD void operator()(uint32_t g) const {
+        const uint32_t c = c0 + g / Bpad, b = g % Bpad;
+        if (b >= B) return;
+        uint32_t first = 0xffffffffu, count = 0;
+        for (uint32_t j = row_chunk[c]; j < row_chunk[c + 1]; j++) {
+            sc acc = sc_zero();
+            for (uint32_t t = row_off[j]; t < row_off[j + 1]; t++) {
+                const uint32_t sw = row_slot[t], slot = sw & 0x3fffffffu;   // the same for every proof of a wavefront: no divergence below
+                const sc x = slot < n3 ? W[(size_t)slot * B + b] : (slot < n3 + m ? v_m[(size_t)(slot - n3) * B + b] : sc_one_mont());
+                if (sw & 0x80000000u) acc = sc_add(acc, x);
+                else if (sw & 0x40000000u) acc = sc_sub(acc, x);
+                else acc = sc_add(acc, sc_mul(x, row_coeff[t]));
+            }
+            if (!sc_is_zero(acc)) {   // the one value-dependent branch: never taken for a satisfied witness
+                if (!count) first = j;
+                count++;
+            }
+        }
+        if (count) check_report(res + 4 * (size_t)b + 1, first, count);
+    }
+};
+
 struct K_tcoef_partial {  // gid = c*B + b -> part[k][c][b], k<6
     const sc* W;     // [5][n][B] a_L a_R a_O s_L s_R
     const sc* wvec;  // wL wR wO

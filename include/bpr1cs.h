@@ -31,6 +31,9 @@
  * address, branch, vote or grid of the commit phase depends on a secret.  Outside that contract in either mode, as upstream or
  * public: the inner-product rounds, the verifier, the witness program (it branches on committed bits, as the reference's gadget
  * code does on the host), the host front-end, compression of the resulting points.  Keccak / STROBE is data-independent.
+ * BPR1CS_OPT_CHECK_WITNESS adds two kernels whose addresses and grids are functions of the circuit and the batch size; their one
+ * value-dependent branch is "this multiplier / row sum is violated", never taken for a satisfied witness and, for a violated
+ * one, revealed by the refusal record anyway.
  * With the option off (the default) every multiscalar multiplication runs through k_msm_fixed2, which (i) gathers table entries at addresses that are the signed digits of
  * the secret scalars (memory-access pattern = secret), (ii) skips a term when the scalars of all 64 proofs of a
  * wavefront are zero, and (iii) takes the a_O wires of Inverse-S-box triples in the form a_O - 1, so that a proof whose
@@ -146,8 +149,9 @@ int bpr1cs_gens_point(const bpr1cs_gens* g, int which, uint32_t i, uint8_t out[3
 int bpr1cs_gens_table_info(const bpr1cs_gens* g, uint32_t* window_bits, uint32_t* windows, uint32_t* format, uint64_t* bytes);
 /* ---- options of a generator handle.  Every option has a default that is the measured optimum on MI355X (what bench.py runs);
  * value < 0 = back to that default.  No process-wide knobs exist: two threads on two handles never see each other's settings.
- * Results (proof bytes, verdicts) never depend on an option, with one exception: BPR1CS_OPT_VERIFY_GROUP_FALLBACK = 0 makes
- * bpr1cs_verify_batch return one verdict per GROUP of proofs (see there). */
+ * Results (proof bytes, verdicts) never depend on an option, with two exceptions: BPR1CS_OPT_VERIFY_GROUP_FALLBACK = 0 makes
+ * bpr1cs_verify_batch return one verdict per GROUP of proofs (see there), and BPR1CS_OPT_CHECK_WITNESS = 1 replaces the bytes of a
+ * proof nobody would accept by a record that says why. */
 #define BPR1CS_OPT_UNFOLD_ROUNDS 0    /* IPA rounds computed from the UN-folded generator tables before the folded generators are
                                          materialised (default: 4 - measured 2 / 3 / 4 / 5 = 2420 / 2748 / 2880 / 2678 proofs/s -, every round for a job of
                                          at most 64 proofs with N x proofs <= 655 360, where a variable-base round is pure latency; clamped to lg N) */
@@ -244,6 +248,31 @@ int bpr1cs_gens_table_info(const bpr1cs_gens* g, uint32_t* window_bits, uint32_t
 #define BPR1CS_VERIFY_GROUP_FALLBACK_NONE 0    /* values of BPR1CS_OPT_VERIFY_GROUP_FALLBACK */
 #define BPR1CS_VERIFY_GROUP_FALLBACK_RECHECK 1
 #define BPR1CS_VERIFY_GROUP_FALLBACK_BISECT 2
+#define BPR1CS_OPT_CHECK_WITNESS 14   /* 0 (default; values < 0 too): off - the prove calls prove whatever they are given, as upstream's
+                                         Prover::prove does: a witness that violates its circuit yields well-formed bytes no verifier
+                                         accepts, and no signal.  1 (any other value means 1): every prove job checks its assignment on
+                                         the device before its first commitment sum reads the wires - a_L[i] a_R[i] = a_O[i] for every
+                                         multiplier i, and sum coeff x value = 0 for every constraint j (row j of the description's CSR;
+                                         value(One) = 1, committed values and wires taken as they were handed in or synthesised) - in
+                                         bpr1cs_prove_batch, _transcripts, _draws and _begin / _end, for host wires and for the device
+                                         witness program, on default and BPR1CS_OPT_SECRET_INDEPENDENT handles alike.  A proof whose
+                                         assignment fails is REFUSED: its slot of `proofs_out` holds a refusal record instead of a
+                                         proof (below) and bpr1cs_prove_stats.refused counts it.  Everything else is as with 0: the job
+                                         runs the same launches, every other proof has the same bytes, commitments are written for
+                                         every proof, a transcript handed in ends where it ends today, and the call returns what it
+                                         returns today - one bad witness does not cost the other proofs of a call that is cut into
+                                         jobs.  Costs two short kernels per job (one 32-byte read per constraint term and three per
+                                         multiplier per proof; no multiplication for +-1 coefficients) and, once per circuit, the
+                                         constraints by row on the device: 36 B per term, uploaded by the first checked job (measured:
+                                         DESIGN.md 5.55).  Read once when a prove call starts, like every option */
+/* Refusal record of BPR1CS_OPT_CHECK_WITNESS, bpr1cs_proof_len() bytes like a proof: byte 0 = BPR1CS_PROOF_REFUSED - a version byte
+ * that bpr1cs_proof_parse and every verifier reject (BPR1CS_ERR_FORMAT / verdict 0) -, then little-endian 32-bit words at the
+ * offsets below; every other byte is 0.  0xFFFFFFFF = no multiplier / no constraint is violated. */
+#define BPR1CS_PROOF_REFUSED 0xFF
+#define BPR1CS_REFUSAL_OFF_GATE 4          /* the lowest multiplier i with a_L[i] a_R[i] != a_O[i] */
+#define BPR1CS_REFUSAL_OFF_ROW 8           /* the lowest constraint j with sum coeff x value != 0 */
+#define BPR1CS_REFUSAL_OFF_GATE_COUNT 12   /* number of violated multipliers (saturating) */
+#define BPR1CS_REFUSAL_OFF_ROW_COUNT 16    /* number of violated constraints (saturating) */
 int bpr1cs_gens_set_option(bpr1cs_gens* g, int option, int value);
 /* bpr1cs_gens_create with options: `pairs` = n_pairs x (option, value).  BPR1CS_ERR_INVALID_ARGUMENT for an unknown option. */
 int bpr1cs_gens_create_opts(uint32_t gens_capacity, const int32_t* pairs, size_t n_pairs, bpr1cs_gens** out);
@@ -483,6 +512,7 @@ typedef struct {
     uint64_t sizing_free_bytes;      /* device memory free (+ what the handle and the allocator's cache already hold) when the size was chosen */
     uint64_t sizing_bytes_per_proof; /* working set per proof: own fronts of the jobs in flight + shared front + back phase */
     uint64_t sizing_fixed_bytes;     /* per-job constants, the circuit's merged tables if still to be built, the 4 GiB that must stay free */
+    uint64_t refused;       /* proofs the call refused because their assignment violates the circuit (BPR1CS_OPT_CHECK_WITNESS; 0 while it is off) */
 } bpr1cs_prove_stats;
 int bpr1cs_last_prove_stats(bpr1cs_prove_stats* out);
 

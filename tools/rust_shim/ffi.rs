@@ -85,6 +85,7 @@ pub const BPR1CS_ERR_OUT_OF_MEMORY: i32 = -19;
     pub sizing_free_bytes: u64,
     pub sizing_bytes_per_proof: u64,
     pub sizing_fixed_bytes: u64,
+    pub refused: u64,
 }
 #[link(name = "bpr1cs_hip")]
 extern "C" {
