@@ -51,7 +51,7 @@ struct BpOpts {
     std::atomic<int> job_proofs{0};        // proofs per device job of bpr1cs_prove_batch (0: from the free memory)
     std::atomic<int> jobs_in_flight{2};
     std::atomic<int> host_chain{-1};       // jobs of up to this many proofs run their TranscriptRng chains on host threads (-1: 4 per usable CPU; 0: never)
-    std::atomic<int> host_chain_share{-1}; // percent of a larger job's chains streamed from host threads (-1: 100 for a job that follows another of its call, with AVX-512)
+    std::atomic<int> host_chain_share{-1}; // percent of a larger job's chains streamed from host threads (-1, with AVX-512: what the workers hash beside the job before it, up to 100; for a call's first job the balance against the device chain, host_chain_share_first)
     std::atomic<int> verify_group{0};      // proofs per group of bpr1cs_verify_batch's grouped form (0, 1: off - one mega-check per proof)
     std::atomic<int> verify_group_fallback{1};  // 1: the proofs of a failing group are re-checked one by one, 0: they all get verdict 0, 2: the culprits are found by bisection on the device
     std::atomic<int> check_witness{0};     // 1: every prove job checks its assignment on the device and refuses the proofs that violate the circuit

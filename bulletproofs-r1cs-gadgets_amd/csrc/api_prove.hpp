@@ -32,6 +32,11 @@ struct bpr1cs_job {
     // pinned ring (h_raw) after their RNG states (h_tr0) are read back at ev_head; the rest run in k_rng_stream
     uint32_t Bh = 0;
     dev_event_t ev_head{};
+    // the first job of a call (two_sum in prove_job_begin): draws [0, n + 2) - o_bl, s_bl, s_L - are there while the second half of the
+    // chain is still drawn: the device chain's first leg has ended (ev_rng_half, front stream; reduced on the heavy stream), the
+    // host's first chunks are up and reduced (ev_rng_half_h, witness stream)
+    dev_event_t ev_rng_half{}, ev_rng_half_h{};
+    dev_event_t ev_rng_red{};   // heavy stream: the first leg's draws are reduced (the front stream wipes the raw draws behind it)
 };
 // pinned staging buffers are cached: hipHostFree (like hipFree) synchronises the whole device, which
 // would serialise the in-flight jobs
@@ -73,6 +78,16 @@ static void host_stage_free(void* p) {
     hs.live.erase(it);
 #endif
 }
+// compute units of the current device (k_rng_stream's capacity at one wavefront per SIMD is sized from it)
+static uint32_t dev_cu_count() {
+#if defined(BPR1CS_HOSTSIM)
+    return 256;
+#else
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;   // (0: no share)
+    return cus > 0 ? (uint32_t)cus : 0u;
+#endif
+}
 // diagnostic (include/bpr1cs.h, "Environment"): BPR1CS_DEBUG_JOBS prints host-side timestamps of the job pipeline to stderr
 static bool dbg_jobs() {
     static const bool on = getenv("BPR1CS_DEBUG_JOBS") != nullptr;
@@ -104,7 +119,8 @@ static void job_release(bpr1cs_job* job) {
     for (auto e : job->pt.ev) (void)hipEventDestroy(e);
     job->pt.ev.clear();
 #endif
-    dev_event_t* evs[6] = {&job->ev_in, &job->ev_rng, &job->ev_wit, &job->ev_done, &job->ev_tail, &job->ev_head};
+    dev_event_t* evs[9] = {&job->ev_in, &job->ev_rng, &job->ev_wit, &job->ev_done, &job->ev_tail, &job->ev_head, &job->ev_rng_half, &job->ev_rng_half_h,
+                           &job->ev_rng_red};
     for (auto e : evs) dev_event_destroy(e);
     for (void* p : job->deferred) dev_free_now(p);
     job->deferred.clear();
@@ -188,7 +204,8 @@ static void enqueue_witness_check(const bpr1cs_circuit* c, const sc* W, const sc
 // Transcript::new(label) gives) or n_init = batch (the caller's own); want_tr: read the final transcript states back.
 static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const strobe* init, size_t n_init, bool want_tr,
                            const uint8_t* values, const uint8_t* v_blindings, const uint8_t* rng_seeds,
-                           const uint8_t* wires, size_t batch, bpr1cs_job** job_out, const uint8_t* ext_draws = nullptr, int auto_share = 0) {
+                           const uint8_t* wires, size_t batch, bpr1cs_job** job_out, const uint8_t* ext_draws = nullptr, int auto_share = 0,
+                           bool first_of_call = false) {
     // ext_draws (bpr1cs_prove_batch_draws): the caller has appended Prover::new's and commit's transcript messages and "m" itself - `init` holds
     // one transcript per proof in that state - and has run the proof's TranscriptRng: batch x (2n + 8) raw 64-byte draws
     if (!g || !c || !init || (!rng_seeds && !ext_draws) || !job_out || batch == 0 || (n_init != 1 && n_init != batch)) return BPR1CS_ERR_INVALID_ARGUMENT;
@@ -305,8 +322,9 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     // The split (BPR1CS_OPT_HOST_CHAIN_SHARE): in a job that follows another job of its call, the chains run beside that job's
     // sums - k_rng_stream took ~9 % of the GPU's kernel time beside them and slowed the A_I / S launches by 80 ms a job -
     // while the host's cores sit idle.  auto_share: what bpr1cs_prove_batch chose for this job (host_chain_share_auto: the part the
-    // host's budget - 1 workers hash within the heavy stream's time per job; 0 for the first job of a call).  No split without a
-    // worker: the calling thread only hands the chunks over.
+    // host's budget - 1 workers hash within the heavy stream's time per job; for the first job of a call, whose chains nothing hides,
+    // host_chain_share_first: the part that lets the host and the device end together).  No split without a worker: the calling
+    // thread only hands the chunks over.
     uint32_t Bh = 0;
     const unsigned chain_workers = host_cpu_budget() - 1;
 #if !defined(BPR1CS_HOSTSIM)
@@ -317,6 +335,18 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     }
 #endif
     job->Bh = Bh;
+    // The first job of a call is the only one whose heavy stream waits for the chain (a later job's chain ends while the job before it
+    // is summed), and S1's first half, <s_L, G>, needs only the first n + 2 draws: the chain runs in two legs, cut behind draw n + 1,
+    // each reduced when it ends, and S1 is summed in two launches, the first behind the chain's second leg.  Point
+    // addition is exact: the same S1.  Not for a job of a few proofs (one launch for the three finishes), a secret-independent handle
+    // (S1 shares its launch with the blinding terms) or the caller's own draws.
+#if defined(BPR1CS_HOSTSIM)
+    const bool two_sum = false;
+    (void)first_of_call;
+#else
+    const bool two_sum = first_of_call && !ext && !host_chain && n > 0 && B > SMALL_JOB_PROOFS && !g->ct();
+#endif
+    const uint32_t d_half = n + 2;
     {
         ArenaScope sh(shared ? &g->shared_front : &g->front[slot], shared);
         W.alloc((size_t)5 * n * B + 1);
@@ -371,11 +401,23 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
         }
         if (shared) dev_stream_wait(sl, g->rng_free_ev);   // the job before has reduced (and wiped) its raw output
         // split: [2n+7][Bh][8] words of the host's proofs first, then [2n+7][B - Bh][8] of the device's (each part contiguous per draw)
-        if (Bh < B) {
-            hipLaunchKernelGGL(k_rng_stream, dim3((B - Bh + 1) / 2), dim3(64), 0, sl, rng.p + Bh, rng_raw.p + (size_t)draws * Bh * 8, rng_err.p, B - Bh, draws);
+        if (Bh < B && two_sum) {
+            // two legs, one behind the other: the first leaves its states where it found them.  Its draws are reduced on the HEAVY stream,
+            // in front of the sum that needs them (sum_first_half below): between the legs the reduction would have to find room on a
+            // GPU full of the A_I / A_O sum's waves and held the second leg back by 42 ms in a trace
+            const uint32_t Bd = B - Bh;
+            uint64_t* raw_d = rng_raw.p + (size_t)draws * Bh * 8;
+            hipLaunchKernelGGL(k_rng_stream, dim3((Bd + 1) / 2), dim3(64), 0, sl, rng.p + Bh, raw_d, rng_err.p, Bd, d_half, rng.p + Bh);
+            HIPCHK(hipGetLastError());
+            dev_event_create(&job->ev_rng_half);
+            dev_event_record(job->ev_rng_half, sl);
+            hipLaunchKernelGGL(k_rng_stream, dim3((Bd + 1) / 2), dim3(64), 0, sl, rng.p + Bh, raw_d + (size_t)d_half * Bd * 8, rng_err.p, Bd, draws - d_half, (strobe*)nullptr);
+            HIPCHK(hipGetLastError());
+        } else if (Bh < B) {
+            hipLaunchKernelGGL(k_rng_stream, dim3((B - Bh + 1) / 2), dim3(64), 0, sl, rng.p + Bh, rng_raw.p + (size_t)draws * Bh * 8, rng_err.p, B - Bh, draws, (strobe*)nullptr);
             HIPCHK(hipGetLastError());
         }
-        if (!Bh) {
+        if (!Bh && !two_sum) {   // (two_sum: in finish_split, behind the first sum's reduction of the first leg)
             if (shared) dev_stream_wait(sl, g->w_free_ev);     // s_L / s_R live in W: the job before is past its l(x), r(x)
             launch((uint64_t)draws * B, K_rng_reduce{rng_raw.p, blind.p, sL, sR, B, n, 0u}, sl);
             dev_zero(rng_raw.p, rng_raw.bytes(), sl);  // raw blinding material
@@ -383,7 +425,7 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
             if (shared) dev_event_record(g->rng_free_ev, sl);
         }
 #endif
-        if (!Bh) dev_event_record(job->ev_rng, sl);
+        if (!Bh && !two_sum) dev_event_record(job->ev_rng, sl);
     }
 
     if (host_chain) {
@@ -456,8 +498,23 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     // the split's host part, where the heavy stream is about to wait for the draws (in front of S1): the chains stream in chunks of
     // 256 draws through a ring of 4 pinned slots (64 MiB each at 4096 proofs) on the job's witness stream - a copy engine's work, the
     // heavy stream never waits for a copy - into the host part of rng_raw; both parts are reduced on the front stream after it
-    auto finish_split = [&]() {
-        if (!Bh) return;
+    // at_half (two_sum): called once the host part's first range is on its way - from inside the hand-over of the chunk that holds
+    // draw n + 1, while the workers hash on - or at once when there is no host part
+    auto finish_split = [&](const std::function<void()>& at_half) {
+        if (!Bh) {
+            if (!at_half) return;
+            // two_sum, every chain on the device: the first sum goes in (it reduces the first leg's draws on the heavy stream), then
+            // the second range and the wipes, which must not overtake that reduction
+            at_half();
+            if (shared) dev_stream_wait(sl, g->w_free_ev);
+            launch((uint64_t)(draws - d_half) * B, K_rng_reduce{rng_raw.p, blind.p, sL, sR, B, n, 0u, 0u, 0u, d_half}, sl);
+            if (job->ev_rng_red) dev_stream_wait(sl, job->ev_rng_red);
+            dev_zero(rng_raw.p, rng_raw.bytes(), sl);
+            dev_zero(rng.p, rng.bytes(), sl);
+            if (shared) dev_event_record(g->rng_free_ev, sl);
+            dev_event_record(job->ev_rng, sl);
+            return;
+        }
         const uint32_t Dc = 256, R = 4;
         const dev_stream_t su = job->st3;
         if (!dev_event_sync(job->ev_head)) throw DevError{BPR1CS_ERR_DEVICE};
@@ -474,6 +531,13 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
             [&](uint32_t, uint32_t slot, uint32_t d0, uint32_t nd) {
                 dev_h2d_async(raw_h + (size_t)d0 * Bh * 8, job->h_raw + (size_t)slot * Dc * Bh * 8, (size_t)nd * Bh * 64, su);
                 dev_event_record(ev_slot[slot], su);
+                if (two_sum && d0 <= d_half - 1 && d_half - 1 < d0 + nd) {   // draws [0, n + 2) of the host's chains are up: o_bl, s_bl, all of s_L
+                    if (shared) dev_stream_wait(su, g->w_free_ev);
+                    launch((uint64_t)d_half * Bh, K_rng_reduce{raw_h, blind.p, sL, sR, B, n, 0u, Bh, 0u, 0u}, su);
+                    dev_event_create(&job->ev_rng_half_h);
+                    dev_event_record(job->ev_rng_half_h, su);
+                    if (at_half) at_half();
+                }
             },
             [&](uint32_t slot) { if (!dev_event_sync(ev_slot[slot])) throw DevError{BPR1CS_ERR_DEVICE}; }, chain8_select(), &busy_us);
         if (ok && busy_us > 0) host_chain_rate_cell().store(busy_us / ((double)Bh * draws));   // (the next jobs' share is sized from it)
@@ -483,15 +547,17 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
         dev_event_record(job->ev_head, su);
         dev_stream_wait(sl, job->ev_head);
         if (shared) dev_stream_wait(sl, g->w_free_ev);
-        launch((uint64_t)draws * Bh, K_rng_reduce{raw_h, blind.p, sL, sR, B, n, 0u, Bh, 0u}, sl);
-        if (Bh < B) launch((uint64_t)draws * (B - Bh), K_rng_reduce{raw_h + (size_t)draws * Bh * 8, blind.p, sL, sR, B, n, 0u, B - Bh, Bh}, sl);
+        const uint32_t r0 = two_sum ? d_half : 0u;   // (two_sum: the first range of either part is reduced already)
+        launch((uint64_t)(draws - r0) * Bh, K_rng_reduce{raw_h, blind.p, sL, sR, B, n, 0u, Bh, 0u, r0}, sl);
+        if (Bh < B) launch((uint64_t)(draws - r0) * (B - Bh), K_rng_reduce{raw_h + (size_t)draws * Bh * 8, blind.p, sL, sR, B, n, 0u, B - Bh, Bh, r0}, sl);
+        if (job->ev_rng_red) dev_stream_wait(sl, job->ev_rng_red);   // (two_sum: the first leg's draws are reduced on the heavy stream - before the wipe)
         dev_zero(rng_raw.p, rng_raw.bytes(), sl);
         dev_zero(rng.p, rng.bytes(), sl);
         if (shared) dev_event_record(g->rng_free_ev, sl);
         dev_event_record(job->ev_rng, sl);
     };
-    auto finish_host_chains = [&]() {
-        finish_split();
+    auto finish_host_chains = [&](const std::function<void()>& at_half = nullptr) {
+        finish_split(at_half);
         if (!host_chain) return;
         chains.wait();
         DBG_JOB("begin: host chain(s) done");
@@ -579,7 +645,28 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
             finI.partial = partial.p;
             finI.nchunks = plan.nchunks;
         }
-        finish_host_chains();
+        // two_sum: <s_L, G> goes in behind the first half of the chain, into chunk sums of its own - those of A_I / A_O are live until
+        // their finishes, which need i_bl / o_bl - and outside the arena: the jobs that follow make no such request, and theirs must
+        // keep finding their blocks
+        bool half_summed = false;
+        auto sum_first_half = [&]() {
+            if (half_summed) return;
+            half_summed = true;
+            if (job->ev_rng_half) {   // the device chain's first leg has ended: o_bl, s_bl and s_L of its proofs
+                dev_stream_wait(st, job->ev_rng_half);
+                if (shared) dev_stream_wait(st, g->w_free_ev);     // s_L / s_R live in W: the job before is past its l(x), r(x)
+                launch((uint64_t)d_half * (B - Bh), K_rng_reduce{rng_raw.p + (size_t)draws * Bh * 8, blind.p, sL, sR, B, n, 0u, Bh ? B - Bh : 0u, Bh, 0u}, st);
+                dev_event_create(&job->ev_rng_red);
+                dev_event_record(job->ev_rng_red, st);   // (the front stream wipes the raw draws only behind it)
+            }
+            if (job->ev_rng_half_h) dev_stream_wait(st, job->ev_rng_half_h);
+            ArenaScope own(nullptr);
+            run_msm(g, seg(sL, baseG), none, B, partialS, planS, st, stats);
+            // (its time, terms and additions are counted like any launch's; in bpr1cs_prove_stats.msm_launches S1 stays the ONE sum it
+            // is - seven per job of this shape, which tests/test_gpu_benchconfig.py pins)
+            if (stats && stats->launches) stats->launches--;
+        };
+        finish_host_chains(two_sum ? std::function<void()>(sum_first_half) : std::function<void()>());
         dev_stream_wait(st, job->ev_rng);  // the chain's draws (blindings, s_L, s_R), the transcript after the V's
         pt.mark(st);
         if (ct) {
@@ -609,8 +696,16 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
         } else {
             launch_finish(finI, B, st);
             launch_finish(finO, B, st);
-            run_msm(g, seg(sL, baseG), seg(sR, baseH), B, partial, plan, st, stats);
-            launch_finish(K_msm_finish{g->tab.p, g->tc, partial.p, blind.p + 2 * (size_t)B, nullptr, AOS.p + 2 * (size_t)B * 32, B, plan.nchunks, 1}, B, st);
+            K_msm_finish finS{g->tab.p, g->tc, nullptr, blind.p + 2 * (size_t)B, nullptr, AOS.p + 2 * (size_t)B * 32, B, 0, 1};
+            if (two_sum) {
+                // <s_R, H> into the block the uncut sum would take (and of its size: the arena's request sequence is that of every job)
+                const size_t need = msm_partial_need(g, 2 * n, B);
+                if (partial.n < need) partial.alloc(need);
+                run_msm(g, seg(sR, baseH), none, B, partial, plan, st, stats);
+                finS.partial_b = partialS.p; finS.nchunks_b = planS.nchunks;
+            } else run_msm(g, seg(sL, baseG), seg(sR, baseH), B, partial, plan, st, stats);
+            finS.partial = partial.p; finS.nchunks = plan.nchunks;
+            launch_finish(finS, B, st);
         }
         }
     }
@@ -917,8 +1012,9 @@ static int prove_batch_impl(const bpr1cs_gens* g, const bpr1cs_circuit* c, const
     };
     size_t done = 0;
     bool retried = false;
-    // the default host share of the next job (BPR1CS_OPT_HOST_CHAIN_SHARE = -1, csrc/host_chain.hpp host_chain_share_auto): none for the
-    // first job of the call; for a job that follows another, what the host hashes in 3/4 of the heavy stream's time for the job before
+    // the default host share of the next job (BPR1CS_OPT_HOST_CHAIN_SHARE = -1, csrc/host_chain.hpp): for the first job of the call, whose
+    // chains run in the open, the part that lets host and device end together (host_chain_share_first: none up to one wavefront per
+    // SIMD); for a job that follows another (host_chain_share_auto), what the host hashes in 3/4 of the heavy stream's time for the job before
     // it - its multiscalar time per proof measured so far in this call, else in the last call of this circuit on this handle, else the
     // device chain's own length (2.5 us per permutation: the job before runs it in front of its sums)
     double prior_ms_per_proof = 0;
@@ -928,8 +1024,13 @@ static int prove_batch_impl(const bpr1cs_gens* g, const bpr1cs_circuit* c, const
         if (it != c->mt.end()) prior_ms_per_proof = it->second->msm_ms_per_proof;
     }
     auto auto_share = [&](size_t take) -> int {
-        if (fl.empty() || ext_draws || g->opts.host_chain_share.load() >= 0) return 0;
+        if (ext_draws || g->opts.host_chain_share.load() >= 0) return 0;
         const uint32_t draws = 2 * c->n + 7;
+        if (fl.empty()) {   // nothing in front of the job: the host takes what lets both parts end together (k_rng_stream: one wavefront per SIMD, two proofs each)
+            const unsigned workers = host_cpu_budget() - 1;
+            const double us = std::max(host_chain_us_per_perm(), workers * HOST_CHAIN_STREAM_US_PER_PERM);   // (hashed AND streamed to the device)
+            return host_chain_share_first(chain8_select() != chain8_advance_scalar, take, draws, workers, us, 2u * 4u * dev_cu_count(), DEV_CHAIN_US_PER_PERM);
+        }
         const size_t before = fl.back().job->B;
         const double per_proof = ended && acc.msm_ms > 0 ? acc.msm_ms / ended : prior_ms_per_proof;
         const double deadline_ms = per_proof > 0 ? per_proof * before : draws * 2.5e-3;
@@ -954,7 +1055,7 @@ static int prove_batch_impl(const bpr1cs_gens* g, const bpr1cs_circuit* c, const
         else e = prove_job_begin(g, c, n_init == 1 ? init : init + done, n_init == 1 ? 1 : take, tr_out != nullptr,
                                  values ? values + done * m * 32 : nullptr, v_blindings ? v_blindings + done * m * 32 : nullptr,
                                  rng_seeds ? rng_seeds + done * 32 : nullptr, wires ? wires + done * wn * 32 : nullptr, take, &job,
-                                 ext_draws ? ext_draws + done * (2 * (size_t)c->n + 8) * 64 : nullptr, auto_share(take));
+                                 ext_draws ? ext_draws + done * (2 * (size_t)c->n + 8) * 64 : nullptr, auto_share(take), fl.empty());
         if (e == BPR1CS_ERR_OUT_OF_MEMORY && (take > 64 || !retried)) {
             // out of memory: let the jobs in flight finish and hand the scratch back (arenas sized for the smaller jobs of an
             // earlier call sit next to the blocks that replace them until their last user has drained) - then the same job once

@@ -159,7 +159,8 @@ static chain8_fn chain8_select(bool allow_avx512 = true) {
     return chain8_advance_scalar;
 }
 
-// How much of a job the host takes by default (BPR1CS_OPT_HOST_CHAIN_SHARE = -1), in percent.  The host's part must be hashed before
+// How much of a job THAT FOLLOWS ANOTHER JOB OF ITS CALL the host takes by default (BPR1CS_OPT_HOST_CHAIN_SHARE = -1), in percent (the
+// call's first job: host_chain_share_first below).  The host's part must be hashed before
 // the heavy stream reaches the job's S sum, i.e. while it works through the job before: `deadline_ms`, the heavy stream's time per job
 // measured so far in the call (its multiscalar launches, HIP-event timed).  The whole job costs B x draws x us_per_perm / workers of
 // wall time on `workers` threads; the share is what fits into 3/4 of the deadline, at most 100.  None without the eight-way chain
@@ -171,6 +172,42 @@ static int host_chain_share_auto(bool eight_way, uint64_t B, uint32_t draws, uns
     const double whole_ms = (double)B * draws * us_per_perm / workers / 1e3;
     const double share = 100.0 * 0.75 * deadline_ms / whole_ms;
     return share >= 100.0 ? 100 : (int)share;
+}
+// The FIRST job of a call has no job before it to hide its chains behind: the device chain runs in the open, in front of the job's
+// S sum, and the host's workers would idle.  Its default share is what makes both parts end together:
+//   T_dev(Bd)  = draws x dev_us_per_perm x max(1, Bd / dev_cap)   k_rng_stream: latency-bound (one chain's own length) up to dev_cap
+//                                                                 proofs - one wavefront on every SIMD, two proofs each - and
+//                                                                 throughput-bound (LDS) above (profiles/r12a_call_start.txt)
+//   T_host(Bh) = Bh x draws x us_per_perm / workers
+// -> the Bh that minimises max(T_dev(B - Bh), T_host(Bh)): the balance point of the throughput-bound regime, and no more than
+// B - dev_cap (below dev_cap the device part gets no shorter).  None for B <= dev_cap (the device chain is at its latency floor
+// already), without the eight-way chain or HOST_SHARE_MIN_WORKERS workers, or when the model saves less than a tenth of T_dev(B).
+// dev_us_per_perm on MI355X, for the depth-32 circuit's 37 319 draws (profiles/r12a_call_start.txt): the kernel alone on the chip takes
+// 89.0 ms with one wavefront (2.38 us), 108.8 ms at 2048 proofs, 132.6 at 3072 and 154.0 at 4096 (2.06 us x 4096 / 2048); inside a
+// call, next to the witness kernel and the A_I / A_O sums, 182 - 207 ms at 4096 (2.44 - 2.77 us x 2).  2.5 us: the model's line
+// through the origin then balances at 39 % for 15 workers, where the measured line of the kernel alone (63.7 ms + 0.0220 ms per
+// proof) balances at 40 %.
+// Nor for a short chain: a split reads the states back, starts the workers and streams through the pinned ring - a millisecond or two
+// that a circuit of a few dozen multipliers (a 7-bit bound check: 33 draws, 0.2 ms of chain for 4096 proofs) never earns back.
+static const double DEV_CHAIN_US_PER_PERM = 2.5;
+static const double HOST_SHARE_FIRST_MIN_SAVED_US = 2000.0;
+// What the workers hash also has to reach the device: 64 bytes per draw and proof through the pinned ring and over the link.  In a
+// trace of a first job with 1597 host chains (profiles/r12a_call_start.txt) the second half of their draws - 18 659 draws x 1597 proofs
+// - took 79.8 ms to arrive: 0.0027 us per permutation and proof (24 GB/s), where 15 workers hash one in 0.0019.  The caller of
+// host_chain_share_first counts a worker's rate only down to this floor times the workers.
+static const double HOST_CHAIN_STREAM_US_PER_PERM = 0.0027;
+static int host_chain_share_first(bool eight_way, uint64_t B, uint32_t draws, unsigned workers, double us_per_perm, uint32_t dev_cap,
+                                  double dev_us_per_perm) {
+    if (!eight_way || workers < HOST_SHARE_MIN_WORKERS || B == 0 || draws == 0 || !(us_per_perm > 0) || !(dev_us_per_perm > 0) || dev_cap == 0) return 0;
+    if (B <= dev_cap) return 0;
+    const double dev_rate = dev_us_per_perm / dev_cap, host_rate = us_per_perm / workers;   // us per permutation and proof of each side
+    const uint64_t balance = (uint64_t)((double)B * dev_rate / (dev_rate + host_rate));
+    const uint64_t Bh = std::min<uint64_t>(balance, B - dev_cap);
+    const double t_all = (double)draws * dev_rate * (double)B;
+    const double t_dev = (double)draws * dev_rate * (double)(B - Bh), t_host = (double)Bh * draws * host_rate;   // (B - Bh >= dev_cap)
+    const double saved = t_all - std::max(t_dev, t_host);
+    if (saved < 0.1 * t_all || saved < HOST_SHARE_FIRST_MIN_SAVED_US) return 0;
+    return (int)((100 * Bh + B / 2) / B);
 }
 // Microseconds per permutation and chain of one worker of the eight-way chain: measured once on the calling thread (eight chains, 256
 // draws: ~0.1 ms) with a 25 % margin for the workers sharing the package, then replaced by what each streamed job measured.

@@ -298,8 +298,10 @@ struct K_rng_reduce {  // [i_bl,] o_bl, s_bl, s_L[n], s_R[n], t1 t3 t4 t5 t6 bli
     sc* sR;
     uint32_t B, n, lead;
     uint32_t Bc = 0, b0 = 0;
+    uint32_t d0 = 0;   // lead = 0: the launch covers the draws from d0 on (a chain reduced in two ranges: gid = (d - d0) * B + b)
     HD void operator()(uint32_t g) const {
         uint32_t d, b;
+        if (!lead) g += d0 * (Bc ? Bc : B);
         if (lead) {
             b = g / (2 * n + 8); d = g % (2 * n + 8);
         } else if (Bc) {

@@ -551,7 +551,9 @@ __device__ inline void lds_order() { __syncthreads(); }  // one wavefront per wo
 // barrier pins the convergence point.  tests/test_gpu_parity.py::test_rng_chain_matches_oracle stays the gate that the
 // blinding stream is byte-identical for every compiler version.
 #define LDS_HANDOFF() do { __atomic_signal_fence(__ATOMIC_SEQ_CST); __builtin_amdgcn_wave_barrier(); __atomic_signal_fence(__ATOMIC_SEQ_CST); } while (0)
-__global__ void __launch_bounds__(64) k_rng_stream(const strobe* rng_in, uint64_t* raw_out, int* err, uint32_t B, uint32_t draws) {
+// rng_out (may be rng_in's own block, or null): where a launch that makes only the first `draws` of a chain leaves each state, still
+// the steady one, for the launch that makes the rest - that one gets raw_out advanced by the draws already made (x B x 8 words).
+__global__ void __launch_bounds__(64) k_rng_stream(const strobe* rng_in, uint64_t* raw_out, int* err, uint32_t B, uint32_t draws, strobe* rng_out) {
     // one long dependent chain per state: take every issue slot it can use.  (Round 4 measured the wave priorities of the two front
     // kernels - (chain, witness) = (3,2) / (0,0) / (1,1) / (3,0) / (0,2): 2951 / 2945 / 2934 / 2941 / 2932 proofs/s on a box whose clock
     // sagged 0.7 % over the series - what the front costs the co-running sums (+5 % on their launches) is its work, not the arbitration.)
@@ -619,6 +621,10 @@ __global__ void __launch_bounds__(64) k_rng_stream(const strobe* rng_in, uint64_
             if (valid) raw_out[((size_t)d * B + b) * 8 + i] = a;
             a = 0;  // prf squeeze zeroes the bytes it returns
         }
+    }
+    if (rng_out && valid) {   // (a wavefront's two halves own two different proofs; the mirror lanes 25..31 write nothing)
+        if (real) rng_out[b].st[j] = a;
+        if (i == 0) { const uint32_t f = rng_in[b].cur_flags; rng_out[b].pos = 64; rng_out[b].pos_begin = 0; rng_out[b].cur_flags = f; }
     }
 #undef LO
 #undef HI

@@ -403,6 +403,15 @@ static void run_commit_ct(const bpr1cs_gens* g, const sc* s0, const sc* s1, uint
     run_msm_multi(g, &q, 1, count, st, stats, nullptr, true);
     launch(count, K_ct_finish{partial.p, plan.nchunks, count, out, B, m}, st);
 }
+// the points a `total`-term request of run_msm_multi's wavefront path (B > MSM_LANE_PATH_MAX_PROOFS, no chunk hint, not ct) asks of
+// its `partial` block: a caller that cuts one sum into two keeps the arena's request sequence of the uncut sum with it
+static size_t msm_partial_need(const bpr1cs_gens* g, uint32_t total, uint32_t B) {
+    uint32_t chunk, nchunks = pick_chunks(total, B, 1u << g->opts.msm_threads_log2.load(), chunk);
+    if (chunk < 8 && total >= 8) nchunks = (total + 7) / 8;
+    const uint32_t l1 = nchunks > MSM_REDUCE_GROUP ? (nchunks + MSM_REDUCE_GROUP - 1) / MSM_REDUCE_GROUP : 0;
+    const uint32_t l2 = l1 > MSM_REDUCE_GROUP ? (l1 + MSM_REDUCE_GROUP - 1) / MSM_REDUCE_GROUP : 0;
+    return ((size_t)nchunks + l1 + l2) * B;
+}
 static void run_msm(const bpr1cs_gens* g, MsmSeg s0, MsmSeg s1, uint32_t B, DevBuf<ge>& partial, MsmPlan& plan, dev_stream_t st,
                     MsmStats* stats, const uint8_t* table = nullptr) {
     MsmReq q{s0, s1, &partial, &plan, table};

@@ -182,9 +182,12 @@ int bpr1cs_gens_table_info(const bpr1cs_gens* g, uint32_t* window_bits, uint32_t
                                          on a secret, ever runs on the host */
 #define BPR1CS_OPT_HOST_CHAIN_SHARE 10 /* measuring option: percent (0..100) of a large job's proofs whose TranscriptRng chains run on host threads,
                                          eight proofs per AVX-512 register set, streamed to the device in chunks of draws while the rest run
-                                         in k_rng_stream.  Default (-1), per job of bpr1cs_prove_batch: none for the first job of a call (it
-                                         has nothing to hide behind), none without AVX-512 or with fewer than 2 worker threads (the process
-                                         may use budget - 1 of its usable CPUs: affinity mask, cgroup quota); otherwise the share the workers
+                                         in k_rng_stream.  Default (-1), per job of bpr1cs_prove_batch: none without AVX-512 or with fewer than 2 worker threads
+                                         (the process may use budget - 1 of its usable CPUs: affinity mask, cgroup quota).  The first job of
+                                         a call has nothing to hide its chains behind: the host takes the part that lets its workers and the
+                                         device end together (~39 % of 4096 depth-32 proofs on 15 workers), and none of a job that leaves the
+                                         device at most one wavefront per SIMD (2 proofs each: 2048 on MI355X) or whose chains are too short
+                                         to earn the hand-over back.  A job that follows another: the share the workers
                                          hash in 3/4 of the heavy stream's time per job measured so far in the call (its multiscalar
                                          launches; before any job has ended, the length of the device chain), at the rate the workers last
                                          measured - e.g. 100 % of a 4096-proof depth-32 job on 15 workers, ~55 % on 3.  A pinned share is
