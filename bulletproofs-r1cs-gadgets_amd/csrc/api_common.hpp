@@ -218,9 +218,23 @@ struct bpr1cs_circuit {
         uint32_t job_epoch = 0;    // ... while the handle's sizing_epoch is the one it was chosen under
         double msm_ms_per_proof = 0;   // heavy-stream multiscalar time per proof of the last bpr1cs_prove_batch (the default host share of its chains)
         uint64_t sz_avail = 0, sz_per_proof = 0, sz_fixed = 0;   // what that choice was made from (bpr1cs_prove_stats.sizing_*)
+        bool tables_for(const bpr1cs_gens* g) const { return tab.p && W == g->tc.W && cap == g->cap; }
+        bool hs_for(const bpr1cs_gens* g) const { return hs_tab.p && hs_W == g->tc.W && hs_cap == g->cap; }
+        bool sized_in(uint32_t epoch) const { return job_epoch == epoch; }
     };
     mutable std::mutex mt_mu;
     mutable std::map<const bpr1cs_gens*, MergedTab*> mt;
+    // the record of (this circuit, handle g): null if there is none / made if there is none.  Under mt_mu: the caller's guard is the ticket.
+    using Lock = std::lock_guard<std::mutex>;
+    MergedTab* tab_find(const bpr1cs_gens* g, const Lock&) const {
+        auto it = mt.find(g);
+        return it == mt.end() ? nullptr : it->second;
+    }
+    MergedTab& tab_of(const bpr1cs_gens* g, const Lock&) const {
+        MergedTab*& t = mt[g];
+        if (!t) t = new MergedTab();
+        return *t;
+    }
     // BPR1CS_OPT_CHECK_WITNESS: the constraints BY ROW (the arrays above hold them by wire slot), built by bpr1cs_circuit_create on the
     // host and uploaded under mt_mu by the first checked job of the circuit - a circuit that is never checked holds none of it on the
     // device.  Per entry a slot word (the flattening's numbering, bits 31 / 30 = coefficient +1 / -1 as in ent_row) and a Montgomery

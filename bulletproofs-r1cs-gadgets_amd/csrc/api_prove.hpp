@@ -32,7 +32,7 @@ struct bpr1cs_job {
     // pinned ring (h_raw) after their RNG states (h_tr0) are read back at ev_head; the rest run in k_rng_stream
     uint32_t Bh = 0;
     dev_event_t ev_head{};
-    // the first job of a call (two_sum in prove_job_begin): draws [0, n + 2) - o_bl, s_bl, s_L - are there while the second half of the
+    // the first job of a call (the two-leg sources of csrc/prove_draws.hpp): draws [0, n + 2) - o_bl, s_bl, s_L - are there while the second half of the
     // chain is still drawn: the device chain's first leg has ended (ev_rng_half, front stream; reduced on the heavy stream), the
     // host's first chunks are up and reduced (ev_rng_half_h, witness stream)
     dev_event_t ev_rng_half{}, ev_rng_half_h{};
@@ -100,6 +100,7 @@ static double dbg_ms() {
 #define DBG_JOB(...) do { if (dbg_jobs()) { fprintf(stderr, "bpr1cs[%9.2f ms] ", dbg_ms()); fprintf(stderr, __VA_ARGS__); fputc('\n', stderr); } } while (0)
 // secrets in host memory: a plain memset in front of a free is a dead store the compiler may drop
 static void host_wipe(void* p, size_t n) { explicit_bzero(p, n); }   // (a volatile byte loop here was 9 ms of a depth-253 proof: its 18 MB of draws)
+#include "prove_draws.hpp"
 // wait for everything a job has enqueued and release what it holds (normal end and error paths)
 static void job_wait(bpr1cs_job* job) {
     if (!job) return;
@@ -167,7 +168,7 @@ static int prove_job_fail(const bpr1cs_gens* g, bpr1cs_job* job, uint32_t slot, 
         const dev_stream_t st = g->jstream[slot][1];
         g->front[slot].wipe(st);
         if (g->in_flight.load() == 0) { g->shared_front.wipe(st); g->arena.wipe(st); }
-        for (void* p : job->deferred) (void)p;   // (blocks replaced while enqueuing: too small to have been written by this job's kernels)
+        // (job->deferred, the blocks replaced while enqueuing: too small to have been written by this job's kernels)
         dev_sync(st);
     } catch (...) {}
     job_release(job);
@@ -285,12 +286,13 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     }
     DevBuf<uint8_t> d_in(job->h_in_bytes);
     dev_h2d_async(d_in.p, job->h_in, job->h_in_bytes, sl);
-    struct { sc* p; } v_raw{(sc*)d_in.p}, vbl_raw{(sc*)d_in.p + (size_t)m * B};
-    struct { uint8_t* p; } d_seeds{d_in.p + 2 * vb};
-    struct { strobe* p; } d_init{(strobe*)(d_in.p + 2 * vb + sb)};
+    sc* v_raw = (sc*)d_in.p;
+    sc* vbl_raw = (sc*)d_in.p + (size_t)m * B;
+    uint8_t* d_seeds = d_in.p + 2 * vb;
+    strobe* d_init = (strobe*)(d_in.p + 2 * vb + sb);
     DevBuf<sc> v_m((size_t)m * B), vbl_m((size_t)m * B);
     const uint32_t init_stride = n_init == 1 ? 0u : 1u;
-    launch((uint64_t)m * B, K_load_inputs{v_raw.p, vbl_raw.p, v_m.p, vbl_m.p}, sl);
+    launch((uint64_t)m * B, K_load_inputs{v_raw, vbl_raw, v_m.p, vbl_m.p}, sl);
 
     DBG_JOB("begin: inputs uploaded");
     // ---- P1: V commitments, transcript, RNG stream
@@ -299,58 +301,30 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     if (ext_draws) {
         dev_zero(Vcomp.p, Vcomp.bytes(), sl);   // (the caller has made the commitments - they are in its transcripts - and this call returns none)
     } else
-    if (g->ct()) run_commit_ct(g, v_raw.p, vbl_raw.p, MSM_CANONICAL, m * B, Vcomp.p, B, m, sl, nullptr);   // (whatever the count: one kernel covers the contract)
+    if (g->ct()) run_commit_ct(g, v_raw, vbl_raw, MSM_CANONICAL, m * B, Vcomp.p, B, m, sl, nullptr);   // (whatever the count: one kernel covers the contract)
     else
 #if !defined(BPR1CS_HOSTSIM)
     if ((uint64_t)m * B <= 256 && m * B > 0) {   // a handful of commitments in front of the transcript chain: a wavefront each (180 -> ~25 us for one proof)
-        hipLaunchKernelGGL(k_commit_wave, dim3(m * B), dim3(64), 0, sl, (const uint8_t*)g->tab.p, g->tc, (const sc*)v_raw.p, (const sc*)vbl_raw.p, Vcomp.p, B, m);
+        hipLaunchKernelGGL(k_commit_wave, dim3(m * B), dim3(64), 0, sl, (const uint8_t*)g->tab.p, g->tc, (const sc*)v_raw, (const sc*)vbl_raw, Vcomp.p, B, m);
         HIPCHK(hipGetLastError());
     } else
 #endif
-    launch((uint64_t)m * B, K_commit_v{g->tab.p, g->tc, v_raw.p, vbl_raw.p, Vcomp.p, B, m}, sl);
+    launch((uint64_t)m * B, K_commit_v{g->tab.p, g->tc, v_raw, vbl_raw, Vcomp.p, B, m}, sl);
     DevBuf<strobe> tr(B);
     const bool shared = g->opts.shared_back.load() != 0;   // jobs in flight share W / the raw RNG output / the back-phase scratch
     DevBuf<sc> blind((size_t)8 * B), W;
     DevBuf<uint64_t> rng_raw;
-    const uint32_t draws = 2 * n + 7;
-    // A small job's TranscriptRng chains run on host threads (csrc/host_chain.hpp): BPR1CS_OPT_HOST_CHAIN_PROOFS, default = jobs of up
-    // to 4 proofs per usable CPU.  One more draw travels then: the chain's first (i_bl), which the device path makes in K_transcript_init.
-    const int o_hc = g->opts.host_chain.load();
-    const bool ext = ext_draws != nullptr;
-    const bool host_chain = !ext && (o_hc < 0 ? B <= 4u * host_cpu_budget() : B <= (uint32_t)o_hc);
-    job->host_chain = host_chain;
-    // The split (BPR1CS_OPT_HOST_CHAIN_SHARE): in a job that follows another job of its call, the chains run beside that job's
-    // sums - k_rng_stream took ~9 % of the GPU's kernel time beside them and slowed the A_I / S launches by 80 ms a job -
-    // while the host's cores sit idle.  auto_share: what bpr1cs_prove_batch chose for this job (host_chain_share_auto: the part the
-    // host's budget - 1 workers hash within the heavy stream's time per job; for the first job of a call, whose chains nothing hides,
-    // host_chain_share_first: the part that lets the host and the device end together).  No split without a worker: the calling
-    // thread only hands the chunks over.
-    uint32_t Bh = 0;
-    const unsigned chain_workers = host_cpu_budget() - 1;
-#if !defined(BPR1CS_HOSTSIM)
-    if (!ext && !host_chain && chain_workers > 0) {
-        const int o_share = g->opts.host_chain_share.load();
-        const int share = o_share >= 0 ? o_share : std::max(0, std::min(100, auto_share));
-        Bh = (uint32_t)(((uint64_t)B * (uint32_t)share + 50) / 100);
-    }
-#endif
-    job->Bh = Bh;
-    // The first job of a call is the only one whose heavy stream waits for the chain (a later job's chain ends while the job before it
-    // is summed), and S1's first half, <s_L, G>, needs only the first n + 2 draws: the chain runs in two legs, cut behind draw n + 1,
-    // each reduced when it ends, and S1 is summed in two launches, the first behind the chain's second leg.  Point
-    // addition is exact: the same S1.  Not for a job of a few proofs (one launch for the three finishes), a secret-independent handle
-    // (S1 shares its launch with the blinding terms) or the caller's own draws.
-#if defined(BPR1CS_HOSTSIM)
-    const bool two_sum = false;
-    (void)first_of_call;
-#else
-    const bool two_sum = first_of_call && !ext && !host_chain && n > 0 && B > SMALL_JOB_PROOFS && !g->ct();
-#endif
-    const uint32_t d_half = n + 2;
+    DevBuf<strobe> rng;
+    // where the job's TranscriptRng draws come from and how they reach blind / s_L / s_R: csrc/prove_draws.hpp
+    JobDraws dr;
+    dr.choose(g, B, n, ext_draws != nullptr, first_of_call, auto_share);
+    const bool two_sum = dr.two_legs();
+    job->host_chain = dr.src == DrawsSource::HostThreads;
+    job->Bh = dr.Bh;
     {
         ArenaScope sh(shared ? &g->shared_front : &g->front[slot], shared);
         W.alloc((size_t)5 * n * B + 1);
-        rng_raw.alloc((size_t)(draws + (host_chain || ext ? 1 : 0)) * B * 8);
+        rng_raw.alloc((size_t)(dr.draws + (dr.lead() ? 1 : 0)) * B * 8);
     }
     sc* sL = W.p + (size_t)3 * n * B;
     sc* sR = W.p + (size_t)4 * n * B;
@@ -360,91 +334,35 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     dev_event_record(job->ev_in, sl);
     DevBuf<int> rng_err(1);
     dev_zero(rng_err.p, sizeof(int), sl);
-    DevBuf<strobe> rng;
-    HostChains chains;   // (joined by its destructor on every path out of this function)
-    if (ext) {
-        // nothing to hash and nothing to wait for: the transcripts are the caller's (past "m"), the draws go up and are reduced at once
-        job->h_raw_bytes = (size_t)(draws + 1) * B * 64;
-        job->h_raw = (uint64_t*)host_stage_alloc(job->h_raw_bytes);
-        memcpy(job->h_raw, ext_draws, job->h_raw_bytes);
-        dev_d2d(tr.p, d_init.p, (size_t)B * sizeof(strobe), sl);
-        if (shared) dev_stream_wait(sl, g->rng_free_ev);
-        dev_h2d_async(rng_raw.p, job->h_raw, job->h_raw_bytes, sl);
-        if (shared) dev_stream_wait(sl, g->w_free_ev);
-        launch((uint64_t)(draws + 1) * B, K_rng_reduce{rng_raw.p, blind.p, sL, sR, B, n, 1u}, sl);
-        dev_zero(rng_raw.p, rng_raw.bytes(), sl);
-        if (shared) dev_event_record(g->rng_free_ev, sl);
-        dev_event_record(job->ev_rng, sl);
-    } else if (host_chain) {
-        // the chains need the V commitments (their compressed encodings are transcript messages): read them back now; the wires go
-        // in and the A_I / A_O sums run on the device while the host hashes
+    dr.job = job; dr.shared = shared;
+    dr.st = st; dr.sl = sl; dr.su = job->st3;
+    dr.rng_raw = &rng_raw; dr.rng = &rng; dr.tr = tr.p; dr.rng_err = rng_err.p;
+    dr.blind = blind.p; dr.sL = sL; dr.sR = sR;
+    if (dr.src == DrawsSource::Caller) {
+        dev_d2d(tr.p, d_init, (size_t)B * sizeof(strobe), sl);   // the transcripts are the caller's (past "m")
+    } else if (dr.src == DrawsSource::HostThreads) {
+        // the chains need the V commitments (their compressed encodings are transcript messages): read them back now
         job->h_V = (uint8_t*)host_stage_alloc((size_t)B * m * 32);
         if (m) dev_d2h_async(job->h_V, Vcomp.p, (size_t)B * m * 32, sl);
-        job->h_raw_bytes = (size_t)(draws + 1) * B * 64;
-        job->h_raw = (uint64_t*)host_stage_alloc(job->h_raw_bytes);
-        job->h_tr0 = (strobe*)host_stage_alloc((size_t)B * sizeof(strobe));
     } else {
-#if defined(BPR1CS_HOSTSIM)
-        // (the simulator runs a kernel's functor proof by proof: the whole chain inside K_transcript_init)
-        launch_transcript(B, K_transcript_init{d_init.p, init_stride, Vcomp.p, vbl_raw.p, d_seeds.p, tr.p, blind.p, sL, sR, nullptr, B, m, n}, sl);
-#else
-        // TranscriptRng on the device: the sequential STROBE chain of a proof (2n + 7 draws, one Keccak-f[1600] each) runs lane-parallel -
-        // one state on 25 lanes, two proofs per wavefront (k_rng_stream) -, the wide reductions mod l of its outputs afterwards in
-        // parallel.  Hidden behind the sums of the job before this one when a batch is cut into jobs.
+#if !defined(BPR1CS_HOSTSIM)
         rng.alloc(B);
-        launch_transcript(B, K_transcript_init{d_init.p, init_stride, Vcomp.p, vbl_raw.p, d_seeds.p, tr.p, blind.p, sL, sR, rng.p, B, m, n}, sl);
-        if (Bh) {   // the host's share: its RNG states go back now (before the device chain is queued on this stream)
-            job->h_tr0 = (strobe*)host_stage_alloc((size_t)Bh * sizeof(strobe));
-            dev_d2h_async(job->h_tr0, rng.p, (size_t)Bh * sizeof(strobe), sl);
-            dev_event_create(&job->ev_head);
-            dev_event_record(job->ev_head, sl);
-        }
-        if (shared) dev_stream_wait(sl, g->rng_free_ev);   // the job before has reduced (and wiped) its raw output
-        // split: [2n+7][Bh][8] words of the host's proofs first, then [2n+7][B - Bh][8] of the device's (each part contiguous per draw)
-        if (Bh < B && two_sum) {
-            // two legs, one behind the other: the first leaves its states where it found them.  Its draws are reduced on the HEAVY stream,
-            // in front of the sum that needs them (sum_first_half below): between the legs the reduction would have to find room on a
-            // GPU full of the A_I / A_O sum's waves and held the second leg back by 42 ms in a trace
-            const uint32_t Bd = B - Bh;
-            uint64_t* raw_d = rng_raw.p + (size_t)draws * Bh * 8;
-            hipLaunchKernelGGL(k_rng_stream, dim3((Bd + 1) / 2), dim3(64), 0, sl, rng.p + Bh, raw_d, rng_err.p, Bd, d_half, rng.p + Bh);
-            HIPCHK(hipGetLastError());
-            dev_event_create(&job->ev_rng_half);
-            dev_event_record(job->ev_rng_half, sl);
-            hipLaunchKernelGGL(k_rng_stream, dim3((Bd + 1) / 2), dim3(64), 0, sl, rng.p + Bh, raw_d + (size_t)d_half * Bd * 8, rng_err.p, Bd, draws - d_half, (strobe*)nullptr);
-            HIPCHK(hipGetLastError());
-        } else if (Bh < B) {
-            hipLaunchKernelGGL(k_rng_stream, dim3((B - Bh + 1) / 2), dim3(64), 0, sl, rng.p + Bh, rng_raw.p + (size_t)draws * Bh * 8, rng_err.p, B - Bh, draws, (strobe*)nullptr);
-            HIPCHK(hipGetLastError());
-        }
-        if (!Bh && !two_sum) {   // (two_sum: in finish_split, behind the first sum's reduction of the first leg)
-            if (shared) dev_stream_wait(sl, g->w_free_ev);     // s_L / s_R live in W: the job before is past its l(x), r(x)
-            launch((uint64_t)draws * B, K_rng_reduce{rng_raw.p, blind.p, sL, sR, B, n, 0u}, sl);
-            dev_zero(rng_raw.p, rng_raw.bytes(), sl);  // raw blinding material
-            dev_zero(rng.p, rng.bytes(), sl);
-            if (shared) dev_event_record(g->rng_free_ev, sl);
-        }
 #endif
-        if (!Bh && !two_sum) dev_event_record(job->ev_rng, sl);
+        launch_transcript(B, K_transcript_init{d_init, init_stride, Vcomp.p, vbl_raw, d_seeds, tr.p, blind.p, sL, sR, rng.p, B, m, n}, sl);
     }
-
-    if (host_chain) {
-        dev_sync(sl);   // the V commitments are on the host
-        DBG_JOB("begin: %u host chain(s) start", B);
-        chains.start(init, n_init, job->h_V, v_blindings, rng_seeds, B, m, n, job->h_tr0, job->h_raw);
-        if ((uint64_t)B * (draws + 1) <= 4096) chains.wait();   // (a few thousand permutations - a bound check's 264 - are done before a thread has started)
-    }
+    dr.enqueue_front(ext_draws);
+    dr.start_host_chains(init, n_init, v_blindings, rng_seeds, m);
 
     // ---- P7/P8: witness (device program) or host-synthesised wires (in a small job: while the host threads hash)
     DevBuf<sc> px;
     // the witness check's result block belongs to the job SLOT, like the slot's arena (the slot's previous job has ended), so two jobs
     // in flight never share it - but it is not one of the arena's blocks: the arena hands them out in request order, and one more
     // request in the middle would make every later block of a job miss its slot whenever the option changes between two calls
-    struct { uint32_t* p; } chk{nullptr};
+    uint32_t* chk = nullptr;
     if (o_check) {
         DevBuf<uint32_t>& blk = g->check_res[slot];
         if (blk.n < (size_t)4 * B) { ArenaScope persistent(nullptr); blk.alloc((size_t)4 * B); }
-        chk.p = blk.p;
+        chk = blk.p;
     }
     if (wires) {
         // Host wires go in on the job's witness stream, as the device program's do: the A_I1 / A_O1 sums need nothing else, so they -
@@ -459,13 +377,13 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
         dev_zero(raw.p, raw.bytes(), sw);
         if (o_check) {
             dev_stream_wait(sw, job->ev_in);   // the committed values in Montgomery form (K_load_inputs, front stream)
-            enqueue_witness_check(c, W.p, v_m.p, chk.p, B, sw);
+            enqueue_witness_check(c, W.p, v_m.p, chk, B, sw);
         }
         dev_event_create(&job->ev_wit);
         dev_event_record(job->ev_wit, sw);
         dev_stream_wait(st, job->ev_wit);
     } else {
-        K_witness kw{c->wops.p, c->lc_off.p, c->lc_var.p, c->lc_coeff.p, v_raw.p, v_m.p, W.p, B, n};
+        K_witness kw{c->wops.p, c->lc_off.p, c->lc_var.p, c->lc_coeff.p, v_raw, v_m.p, W.p, B, n};
         DevBuf<uint8_t> pzf;
         if (c->n_perms) {
             px.alloc((size_t)4 * c->px_stride * B);
@@ -476,7 +394,7 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
 #if defined(BPR1CS_HOSTSIM)
         (void)o_team;
         launch(B, kw, st);
-        if (o_check) enqueue_witness_check(c, W.p, v_m.p, chk.p, B, st);
+        if (o_check) enqueue_witness_check(c, W.p, v_m.p, chk, B, st);
 #else
         int T = o_team;
         if (c->n_perms && (uint32_t)T < c->macro_width + 2) T = 16;  // poseidon_team needs width + 2 lanes
@@ -488,88 +406,12 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
         else if (T == 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_witness_team<8>), dim3(blocks), dim3(64), 0, job->st3, kw);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_witness_team<16>), dim3(blocks), dim3(64), 0, job->st3, kw);
         HIPCHK(hipGetLastError());
-        if (o_check) enqueue_witness_check(c, W.p, v_m.p, chk.p, B, job->st3);
+        if (o_check) enqueue_witness_check(c, W.p, v_m.p, chk, B, job->st3);
         dev_event_create(&job->ev_wit);
         dev_event_record(job->ev_wit, job->st3);
         dev_stream_wait(st, job->ev_wit);
 #endif
     }
-    // the chains' end of the hand-over: called where the heavy stream is about to wait for the draws (in front of S1)
-    // the split's host part, where the heavy stream is about to wait for the draws (in front of S1): the chains stream in chunks of
-    // 256 draws through a ring of 4 pinned slots (64 MiB each at 4096 proofs) on the job's witness stream - a copy engine's work, the
-    // heavy stream never waits for a copy - into the host part of rng_raw; both parts are reduced on the front stream after it
-    // at_half (two_sum): called once the host part's first range is on its way - from inside the hand-over of the chunk that holds
-    // draw n + 1, while the workers hash on - or at once when there is no host part
-    auto finish_split = [&](const std::function<void()>& at_half) {
-        if (!Bh) {
-            if (!at_half) return;
-            // two_sum, every chain on the device: the first sum goes in (it reduces the first leg's draws on the heavy stream), then
-            // the second range and the wipes, which must not overtake that reduction
-            at_half();
-            if (shared) dev_stream_wait(sl, g->w_free_ev);
-            launch((uint64_t)(draws - d_half) * B, K_rng_reduce{rng_raw.p, blind.p, sL, sR, B, n, 0u, 0u, 0u, d_half}, sl);
-            if (job->ev_rng_red) dev_stream_wait(sl, job->ev_rng_red);
-            dev_zero(rng_raw.p, rng_raw.bytes(), sl);
-            dev_zero(rng.p, rng.bytes(), sl);
-            if (shared) dev_event_record(g->rng_free_ev, sl);
-            dev_event_record(job->ev_rng, sl);
-            return;
-        }
-        const uint32_t Dc = 256, R = 4;
-        const dev_stream_t su = job->st3;
-        if (!dev_event_sync(job->ev_head)) throw DevError{BPR1CS_ERR_DEVICE};
-        job->h_raw_bytes = (size_t)R * Dc * Bh * 64;
-        job->h_raw = (uint64_t*)host_stage_alloc(job->h_raw_bytes);
-        if (shared) dev_stream_wait(su, g->rng_free_ev);
-        dev_event_t ev_slot[R] = {};
-        for (uint32_t r = 0; r < R; r++) dev_event_create(&ev_slot[r]);
-        struct Events { dev_event_t* e; uint32_t n; ~Events() { for (uint32_t r = 0; r < n; r++) dev_event_destroy(&e[r]); } } evs_guard{ev_slot, R};
-        uint64_t* raw_h = rng_raw.p;
-        DBG_JOB("begin: %u host chain(s) of %u streamed (%.4f us per permutation and worker)", Bh, B, host_chain_us_per_perm());
-        double busy_us = 0;
-        const bool ok = host_chains_stream(job->h_tr0, Bh, draws, Dc, R, job->h_raw, chain_workers,
-            [&](uint32_t, uint32_t slot, uint32_t d0, uint32_t nd) {
-                dev_h2d_async(raw_h + (size_t)d0 * Bh * 8, job->h_raw + (size_t)slot * Dc * Bh * 8, (size_t)nd * Bh * 64, su);
-                dev_event_record(ev_slot[slot], su);
-                if (two_sum && d0 <= d_half - 1 && d_half - 1 < d0 + nd) {   // draws [0, n + 2) of the host's chains are up: o_bl, s_bl, all of s_L
-                    if (shared) dev_stream_wait(su, g->w_free_ev);
-                    launch((uint64_t)d_half * Bh, K_rng_reduce{raw_h, blind.p, sL, sR, B, n, 0u, Bh, 0u, 0u}, su);
-                    dev_event_create(&job->ev_rng_half_h);
-                    dev_event_record(job->ev_rng_half_h, su);
-                    if (at_half) at_half();
-                }
-            },
-            [&](uint32_t slot) { if (!dev_event_sync(ev_slot[slot])) throw DevError{BPR1CS_ERR_DEVICE}; }, chain8_select(), &busy_us);
-        if (ok && busy_us > 0) host_chain_rate_cell().store(busy_us / ((double)Bh * draws));   // (the next jobs' share is sized from it)
-        host_wipe(job->h_tr0, (size_t)Bh * sizeof(strobe));   // (the RNG states: key material)
-        if (!ok) throw DevError{BPR1CS_ERR_INVALID_ARGUMENT};   // (not the steady STROBE state - k_rng_stream refuses it alike)
-        DBG_JOB("begin: host chain(s) hashed");
-        dev_event_record(job->ev_head, su);
-        dev_stream_wait(sl, job->ev_head);
-        if (shared) dev_stream_wait(sl, g->w_free_ev);
-        const uint32_t r0 = two_sum ? d_half : 0u;   // (two_sum: the first range of either part is reduced already)
-        launch((uint64_t)(draws - r0) * Bh, K_rng_reduce{raw_h, blind.p, sL, sR, B, n, 0u, Bh, 0u, r0}, sl);
-        if (Bh < B) launch((uint64_t)(draws - r0) * (B - Bh), K_rng_reduce{raw_h + (size_t)draws * Bh * 8, blind.p, sL, sR, B, n, 0u, B - Bh, Bh, r0}, sl);
-        if (job->ev_rng_red) dev_stream_wait(sl, job->ev_rng_red);   // (two_sum: the first leg's draws are reduced on the heavy stream - before the wipe)
-        dev_zero(rng_raw.p, rng_raw.bytes(), sl);
-        dev_zero(rng.p, rng.bytes(), sl);
-        if (shared) dev_event_record(g->rng_free_ev, sl);
-        dev_event_record(job->ev_rng, sl);
-    };
-    auto finish_host_chains = [&](const std::function<void()>& at_half = nullptr) {
-        finish_split(at_half);
-        if (!host_chain) return;
-        chains.wait();
-        DBG_JOB("begin: host chain(s) done");
-        dev_h2d_async(tr.p, job->h_tr0, (size_t)B * sizeof(strobe), sl);
-        if (shared) dev_stream_wait(sl, g->rng_free_ev);
-        dev_h2d_async(rng_raw.p, job->h_raw, job->h_raw_bytes, sl);
-        if (shared) dev_stream_wait(sl, g->w_free_ev);
-        launch((uint64_t)(draws + 1) * B, K_rng_reduce{rng_raw.p, blind.p, sL, sR, B, n, 1u}, sl);
-        dev_zero(rng_raw.p, rng_raw.bytes(), sl);
-        if (shared) dev_event_record(g->rng_free_ev, sl);
-        dev_event_record(job->ev_rng, sl);
-    };
     DBG_JOB("begin: front enqueued");
     // ---- P2: A_I1, A_O1, S1.  The sums of A_I1 and A_O1 need the wires only, so they are enqueued BEFORE the heavy stream
     // waits for the TranscriptRng chain (the longer of the two front kernels); their blinding terms and all of S1 follow it.
@@ -604,9 +446,8 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
             TabCfg mtc{};
             {
                 std::lock_guard<std::mutex> lk(c->mt_mu);
-                bpr1cs_circuit::MergedTab*& mt = c->mt[g];
-                if (!mt) mt = new bpr1cs_circuit::MergedTab();
-                if (mt->W != g->tc.W || mt->cap != g->cap || !mt->tab.p) {
+                bpr1cs_circuit::MergedTab* mt = &c->tab_of(g, lk);
+                if (!mt->tables_for(g)) {
                     ArenaScope persistent(nullptr);   // the tables outlive the job (and their construction scratch is a one-off)
                     DevBuf<ge> mp((size_t)2 * T3);
                     launch(T3, K_merge_points{g->pts.p, c->trip.p, mp.p, T3, baseG, baseH}, st);
@@ -648,25 +489,14 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
         // two_sum: <s_L, G> goes in behind the first half of the chain, into chunk sums of its own - those of A_I / A_O are live until
         // their finishes, which need i_bl / o_bl - and outside the arena: the jobs that follow make no such request, and theirs must
         // keep finding their blocks
-        bool half_summed = false;
         auto sum_first_half = [&]() {
-            if (half_summed) return;
-            half_summed = true;
-            if (job->ev_rng_half) {   // the device chain's first leg has ended: o_bl, s_bl and s_L of its proofs
-                dev_stream_wait(st, job->ev_rng_half);
-                if (shared) dev_stream_wait(st, g->w_free_ev);     // s_L / s_R live in W: the job before is past its l(x), r(x)
-                launch((uint64_t)d_half * (B - Bh), K_rng_reduce{rng_raw.p + (size_t)draws * Bh * 8, blind.p, sL, sR, B, n, 0u, Bh ? B - Bh : 0u, Bh, 0u}, st);
-                dev_event_create(&job->ev_rng_red);
-                dev_event_record(job->ev_rng_red, st);   // (the front stream wipes the raw draws only behind it)
-            }
-            if (job->ev_rng_half_h) dev_stream_wait(st, job->ev_rng_half_h);
             ArenaScope own(nullptr);
             run_msm(g, seg(sL, baseG), none, B, partialS, planS, st, stats);
             // (its time, terms and additions are counted like any launch's; in bpr1cs_prove_stats.msm_launches S1 stays the ONE sum it
             // is - seven per job of this shape, which tests/test_gpu_benchconfig.py pins)
             if (stats && stats->launches) stats->launches--;
         };
-        finish_host_chains(two_sum ? std::function<void()>(sum_first_half) : std::function<void()>());
+        dr.deliver(sum_first_half);
         dev_stream_wait(st, job->ev_rng);  // the chain's draws (blindings, s_L, s_R), the transcript after the V's
         pt.mark(st);
         if (ct) {
@@ -731,18 +561,17 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     const bool need_s = r_eff > 0 || (!fvec && lgN > 0);   // product scalars of the un-folded rounds / scalars of the folded generators
     const size_t others = w_bytes + p_bytes + (fvec ? 2 * v_bytes : 0) + (need_s ? 2 * v_bytes : 0);
     DevBuf<uint8_t> shared_blk(std::max(others, vt_count * sizeof(ge_cached)));
-    sc* wvec_p = (sc*)shared_blk.p;
+    sc* wvec = (sc*)shared_blk.p;
     sc* fpart_p = (sc*)(shared_blk.p + w_bytes);
     uint8_t* nxt = shared_blk.p + w_bytes + p_bytes;
-    sc* cG_p = nullptr; sc* cH_p = nullptr; sc* sG_p = nullptr; sc* sH_p = nullptr;
-    if (fvec) { cG_p = (sc*)nxt; cH_p = (sc*)(nxt + v_bytes); nxt += 2 * v_bytes; }
+    sc* cG = nullptr; sc* cH = nullptr; sc* sG_p = nullptr; sc* sH_p = nullptr;
+    if (fvec) { cG = (sc*)nxt; cH = (sc*)(nxt + v_bytes); nxt += 2 * v_bytes; }
     if (need_s) { sG_p = (sc*)nxt; sH_p = (sc*)(nxt + v_bytes); }
-    struct { sc* p; } wvec{wvec_p}, cG{cG_p}, cH{cH_p};
-    run_flatten(c, 3 * n + m, plo.p, phi.p, wvec.p, B, H, st, fpart_p);
+    run_flatten(c, 3 * n + m, plo.p, phi.p, wvec, B, H, st, fpart_p);
     // 4 wavefronts per SIMD: with one (2^16 threads) the kernel is latency bound and a co-running front kernel doubles its time (9 -> 4 ms)
     uint32_t tchunk, TC = pick_chunks(n, B, std::min<uint32_t>(1u << 18, sum_chunk_cap(B, 6) * B), tchunk);
     DevBuf<sc> tpart((size_t)6 * TC * B), tco((size_t)6 * B);
-    launch((uint64_t)TC * B, K_tcoef_partial{W.p, wvec.p, plo.p, phi.p, tpart.p, B, H, n, tchunk, TC}, st);
+    launch((uint64_t)TC * B, K_tcoef_partial{W.p, wvec, plo.p, phi.p, tpart.p, B, H, n, tchunk, TC}, st);
     launch_sum_partials((uint64_t)6 * B, K_sum_partials{tpart.p, tco.p, B, TC}, st);
     if (g->ct()) {
         DevBuf<sc> tsc((size_t)10 * B);
@@ -751,7 +580,7 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
         dev_zero(tsc.p, tsc.bytes(), st);   // (blindings)
     } else
     launch_commit_T(K_commit_T{g->tab.p, g->tc, tco.p, blind.p, Tc.p, B}, B, st);
-    K_transcript_T ktt{tr.p, Tc.p, tco.p, blind.p, wvec.p + (size_t)3 * n * B, vbl_m.p, chal.p, txs.p, B, m, (uint64_t)N};
+    K_transcript_T ktt{tr.p, Tc.p, tco.p, blind.p, wvec + (size_t)3 * n * B, vbl_m.p, chal.p, txs.p, B, m, (uint64_t)N};
     DevBuf<sc> t2b_pre;
 #if !defined(BPR1CS_HOSTSIM)
     if (B <= FINISH_WAVE_MAX_PROOFS && m > 1) {
@@ -763,7 +592,7 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
 #endif
     launch_transcript(B, ktt, st);
     DevBuf<sc> a((size_t)N * B), bb((size_t)N * B);
-    launch((uint64_t)N * B, K_lr_eval{W.p, wvec.p, plo.p, phi.p, chal.p, a.p, bb.p, cG.p, cH.p, B, H, n}, st);
+    launch((uint64_t)N * B, K_lr_eval{W.p, wvec, plo.p, phi.p, chal.p, a.p, bb.p, cG, cH, B, H, n}, st);
     // the wires and blinding vectors are dead: wiped here (upstream: clear_on_drop), and the next job in flight may write its own
     dev_zero(W.p, W.bytes(), st);
     if (shared) dev_event_record(g->w_free_ev, st);
@@ -771,7 +600,7 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
 
     // ---- P5: inner-product argument
     MSM_TRACE_F2_MUTE(1);   // (simulator's recorder: the commit phase ends here)
-    IpaIO io{g, B, N, lgN, (uint32_t)o_unfold, tr.p, a.p, bb.p, cG.p, cH.p, chal.p + (size_t)CH_W * B, nullptr, LR.p, uk.p};
+    IpaIO io{g, B, N, lgN, (uint32_t)o_unfold, tr.p, a.p, bb.p, cG, cH, chal.p + (size_t)CH_W * B, nullptr, LR.p, uk.p};
     // same box, alternating runs: 2957 / 2960 against 2948 / 2955 proofs/s for the depth-32 circuit (the term fetch costs a launch 3.3 ms, the
     // kernel it replaces took 26 ms per job); nothing for N = 512 / 1024 (148.7 against 149.1 k, 83.26 against 83.29 k): from N = 4096 on
     io.fuse_scalars = g->opts.factor_vectors.load() == 3 || (g->opts.factor_vectors.load() == 0 && N >= 4096);
@@ -782,16 +611,15 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
         // a job of a few proofs does not BUILD the table (12 ms of a one-proof call - the reference's tests prove one proof per process -
         // to save 14 112 of round 0's 65 536 lane-terms); it uses one a larger job of this circuit on this handle has built
         std::lock_guard<std::mutex> lk(c->mt_mu);
-        auto it = c->mt.find(g);
-        use_hs = it != c->mt.end() && it->second->hs_tab.p && it->second->hs_W == g->tc.W && it->second->hs_cap == g->cap;
+        const bpr1cs_circuit::MergedTab* mt = c->tab_find(g, lk);
+        use_hs = mt && mt->hs_for(g);
     }
     if (use_hs) {
         // padding structure of round 0 (K_range_sum_points): the table of sum_{n - N/2 <= i < N/2} H_i belongs to
         // (circuit shape, generator handle) and is built by the first job that needs it
         std::lock_guard<std::mutex> lk(c->mt_mu);
-        bpr1cs_circuit::MergedTab*& mt = c->mt[g];
-        if (!mt) mt = new bpr1cs_circuit::MergedTab();
-        if (!mt->hs_tab.p || mt->hs_W != g->tc.W || mt->hs_cap != g->cap) {
+        bpr1cs_circuit::MergedTab* mt = &c->tab_of(g, lk);
+        if (!mt->hs_for(g)) {
             ArenaScope persistent(nullptr);  // the table outlives the job: it must not come from an arena
             DevBuf<ge> part64(64), hsum(1);
             launch(64, K_range_sum_points{g->pts.p, part64.p, baseH + (n - N / 2), baseH + N / 2}, st);
@@ -843,7 +671,7 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     dev_d2h_async(job->h_err, rng_err.p, sizeof(int), st);
     if (o_check) {
         job->h_chk = (uint32_t*)host_stage_alloc((size_t)B * 16);
-        dev_d2h_async(job->h_chk, chk.p, (size_t)B * 16, st);
+        dev_d2h_async(job->h_chk, chk, (size_t)B * 16, st);
     }
     dev_event_create(&job->ev_done);
     dev_event_record(job->ev_done, st);
@@ -932,8 +760,8 @@ static uint32_t auto_job_proofs(const bpr1cs_gens* g, const bpr1cs_circuit* c, b
     size_t fixed = (size_t)5 << 29;   // chunk partial sums of the MSM launches (~2^21 points each, whatever the batch: six buffers in the shared arena), staging
     if (have_program && !c->h_trip.empty() && !g->ct()) {   // (a secret-independent handle takes the plain sums: no merged tables)
         std::lock_guard<std::mutex> lk(c->mt_mu);
-        auto it = c->mt.find(g);
-        if (it == c->mt.end() || !it->second->tab.p) fixed += 2 * c->h_trip.size() * merged_tab_cfg(g, (uint32_t)c->h_trip.size()).base_bytes();
+        const bpr1cs_circuit::MergedTab* mt = c->tab_find(g, lk);
+        if (!mt || !mt->tab.p) fixed += 2 * c->h_trip.size() * merged_tab_cfg(g, (uint32_t)c->h_trip.size()).base_bytes();
     }
     if (check) {   // the circuit's row form, while the first checked job has still to upload it (16 B of result per proof are within `front`'s slack)
         std::lock_guard<std::mutex> lk(c->mt_mu);
@@ -974,28 +802,27 @@ static int prove_batch_impl(const bpr1cs_gens* g, const bpr1cs_circuit* c, const
     // the automatic choice belongs to (circuit, handle) and to the handle's sizing epoch: the same for every call until an option
     // changes, the scratch is released or a call ran out of memory
     JobSizing why;
+    // what the choice was made from (the call that made it, or an earlier one of this circuit on this handle)
+    auto report = [&](const bpr1cs_circuit::MergedTab& mt) { acc.sizing_free_bytes = mt.sz_avail; acc.sizing_bytes_per_proof = mt.sz_per_proof; acc.sizing_fixed_bytes = mt.sz_fixed; };
     auto remember = [&](size_t j) {
-        std::lock_guard<std::mutex> lk(c->mt_mu);
-        bpr1cs_circuit::MergedTab*& mt = c->mt[g];
-        if (!mt) mt = new bpr1cs_circuit::MergedTab();
+        bpr1cs_circuit::Lock lk(c->mt_mu);
+        bpr1cs_circuit::MergedTab& mt = c->tab_of(g, lk);
         const uint32_t ep = g->sizing_epoch.load();
-        if (!mt->job_proofs || mt->job_epoch != ep) { mt->job_proofs = (uint32_t)j; mt->job_epoch = ep; mt->sz_avail = why.avail; mt->sz_per_proof = why.per_proof; mt->sz_fixed = why.fixed; }
-        return (size_t)mt->job_proofs;
+        if (!mt.job_proofs || !mt.sized_in(ep)) { mt.job_proofs = (uint32_t)j; mt.job_epoch = ep; mt.sz_avail = why.avail; mt.sz_per_proof = why.per_proof; mt.sz_fixed = why.fixed; }
+        report(mt);
+        return (size_t)mt.job_proofs;
     };
-    if (automatic) {
-        size_t known = 0;
-        {
-            std::lock_guard<std::mutex> lk(c->mt_mu);
-            auto it = c->mt.find(g);
-            if (it != c->mt.end() && it->second->job_epoch == g->sizing_epoch.load()) known = it->second->job_proofs;
-        }
-        J = known ? known : remember(auto_job_proofs(g, c, wires == nullptr, depth, &why));
-        {   // what the choice was made from (the call that made it, or an earlier one of this circuit on this handle)
-            std::lock_guard<std::mutex> lk(c->mt_mu);
-            auto it = c->mt.find(g);
-            if (it != c->mt.end()) { acc.sizing_free_bytes = it->second->sz_avail; acc.sizing_bytes_per_proof = it->second->sz_per_proof; acc.sizing_fixed_bytes = it->second->sz_fixed; }
+    // what earlier calls of this circuit on this handle have left: the job size (of the current epoch), the multiscalar time per proof
+    size_t known = 0;
+    double prior_ms_per_proof = 0;
+    {
+        bpr1cs_circuit::Lock lk(c->mt_mu);
+        if (const bpr1cs_circuit::MergedTab* mt = c->tab_find(g, lk)) {
+            prior_ms_per_proof = mt->msm_ms_per_proof;
+            if (automatic && mt->sized_in(g->sizing_epoch.load())) { known = mt->job_proofs; report(*mt); }
         }
     }
+    if (automatic) J = known ? known : remember(auto_job_proofs(g, c, wires == nullptr, depth, &why));
     J = std::min(J, grid_max);
     const size_t m = c->m, plen = bpr1cs_proof_len(c), wn = 3 * (size_t)c->n;
     struct Pending { bpr1cs_job* job; size_t first; };
@@ -1017,12 +844,6 @@ static int prove_batch_impl(const bpr1cs_gens* g, const bpr1cs_circuit* c, const
     // SIMD); for a job that follows another (host_chain_share_auto), what the host hashes in 3/4 of the heavy stream's time for the job before
     // it - its multiscalar time per proof measured so far in this call, else in the last call of this circuit on this handle, else the
     // device chain's own length (2.5 us per permutation: the job before runs it in front of its sums)
-    double prior_ms_per_proof = 0;
-    {
-        std::lock_guard<std::mutex> lk(c->mt_mu);
-        auto it = c->mt.find(g);
-        if (it != c->mt.end()) prior_ms_per_proof = it->second->msm_ms_per_proof;
-    }
     auto auto_share = [&](size_t take) -> int {
         if (ext_draws || g->opts.host_chain_share.load() >= 0) return 0;
         const uint32_t draws = 2 * c->n + 7;
@@ -1086,10 +907,8 @@ static int prove_batch_impl(const bpr1cs_gens* g, const bpr1cs_circuit* c, const
     }
     while (!fl.empty()) finish_oldest();
     if (rc == BPR1CS_OK && ended && acc.msm_ms > 0) {
-        std::lock_guard<std::mutex> lk(c->mt_mu);
-        bpr1cs_circuit::MergedTab*& mt = c->mt[g];
-        if (!mt) mt = new bpr1cs_circuit::MergedTab();
-        mt->msm_ms_per_proof = acc.msm_ms / ended;
+        bpr1cs_circuit::Lock lk(c->mt_mu);
+        c->tab_of(g, lk).msm_ms_per_proof = acc.msm_ms / ended;
     }
     tl_last_stats() = acc;
     return rc;

@@ -144,8 +144,7 @@ void bpr1cs_gens_destroy(bpr1cs_gens* g) {
         std::lock_guard<std::mutex> lk(cc.mu);
         for (bpr1cs_circuit* c : cc.items) {
             std::lock_guard<std::mutex> lk2(c->mt_mu);
-            auto it = c->mt.find(g);
-            if (it != c->mt.end()) { delete it->second; c->mt.erase(it); }
+            if (bpr1cs_circuit::MergedTab* mt = c->tab_find(g, lk2)) { delete mt; c->mt.erase(g); }
         }
     }
     g->arena.release();

@@ -39,7 +39,7 @@ int main() {
             const int p = host_chain_share_first(true, B, draws, w, host_us, cap, dev_us);
             if (p < prev) return fail("the share decreases as workers increase", p, prev);
             if (p < 0 || p > 100) return fail("range", p, 0);
-            const uint64_t Bh = (B * (uint64_t)p + 50) / 100;   // as prove_job_begin rounds it
+            const uint64_t Bh = (B * (uint64_t)p + 50) / 100;   // as JobDraws::choose rounds it
             if (p && B - Bh + B / 100 + 1 < cap) return fail("the device part fell below its capacity", (int)(B - Bh), (int)cap);
             if (p) {
                 const double t_all = draws * dr * B, t_dev = draws * dr * (double)(B - Bh), t_host = (double)Bh * draws * host_us / w;

@@ -59,7 +59,7 @@ def _poseidon_cube(oracle, pr):
     n = res[0]["n"]
     assert n == 2 * (48 + pr)
     _REF[pr] = dict(pr=pr, out=out, n=n, values=b"".join(vals), blindings=b"".join(bls), seeds=b"".join(seeds), proofs=[r["proof"] for r in res],
-                    wires=b"".join(r["wires"][:96 * n] for r in res[:65]))
+                    wires=b"".join(r["wires"][:96 * n] for r in res[:65]), comms=[r["comms"] for r in res])
     return _REF[pr]
 
 
@@ -125,6 +125,50 @@ def test_host_wires_first_job_in_two_sums(hip_lib, hip_glib, oracle, gens256, sh
     finally:
         gens256.set_option("host_chain_share", -1)
         gens256.set_option("host_chain_proofs", -1)
+
+
+def test_callers_draws_in_a_call_of_two_jobs(hip_lib, hip_glib, oracle, gens256):
+    """bpr1cs_prove_batch_draws with more than one job in flight: 130 proofs of the n = 128 circuit in jobs of 65, so that the second job's
+    upload and reduction of the caller's draws wait for the first job's events (raw draws wiped, l(x) / r(x) done).  Transcripts as the
+    single-job case of tests/witness_check_cases.py builds them (Prover::new's, commit's and "m" messages); the 2n + 8 draws per proof
+    through the library's own host-side TranscriptRng (bpr1cs_transcript_build_rng, what host/r1cs.hpp's Prover calls: the oracle's
+    Merlin in Python would take 20 s here) - a wrong draw is a proof that differs from the C oracle's."""
+    import ctypes
+    bp = _bp()
+    ref = _poseidon_cube(oracle, 16)
+    circ = bp.CompiledGadget("poseidon_hash_2", [0, 16], [ref["out"]], lib=hip_lib, glib=hip_glib)
+    B, m, n = 130, 6, ref["n"]
+    vp, cp, sz = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t
+    hip_lib.bpr1cs_transcript_build_rng.restype = vp
+    hip_lib.bpr1cs_transcript_build_rng.argtypes = [vp, cp, sz, cp, sz, sz, cp]
+    hip_lib.bpr1cs_transcript_rng_fill_bytes.argtypes = [vp, cp, sz, sz]
+    hip_lib.bpr1cs_transcript_rng_free.argtypes = [vp]
+    hip_lib.bpr1cs_prove_batch_draws.argtypes = [vp, vp, ctypes.POINTER(vp), cp, cp, cp, cp, sz, cp]
+    ts, draws = [], b""
+    for j in range(B):
+        t = bp.Transcript(b"Poseidon_hash_2", lib=hip_lib)
+        t.append_message(b"dom-sep", b"r1cs v1")
+        for c in ref["comms"][j]:
+            t.append_message(b"V", c)
+        t.append_message(b"m", m.to_bytes(8, "little"))
+        rng = hip_lib.bpr1cs_transcript_build_rng(t.h, b"v_blinding", 10, ref["blindings"][32 * m * j:32 * m * (j + 1)], 32, m, ref["seeds"][32 * j:32 * j + 32])
+        buf = ctypes.create_string_buffer(64 * (2 * n + 8))
+        hip_lib.bpr1cs_transcript_rng_fill_bytes(rng, buf, 64, 2 * n + 8)
+        hip_lib.bpr1cs_transcript_rng_free(rng)
+        draws += buf.raw
+        ts.append(t)
+    out = ctypes.create_string_buffer(B * circ.proof_len)
+    gens256.set_option("job_proofs", 65)
+    try:
+        rc = hip_lib.bpr1cs_prove_batch_draws(gens256.h, circ.h, (vp * B)(*[t.h for t in ts]), ref["values"][:B * 32 * m], ref["blindings"][:B * 32 * m], draws, None, B, out)
+        st = bp.last_prove_stats(hip_lib)
+    finally:
+        gens256.set_option("job_proofs", -1)
+    assert rc == 0, rc
+    P = [out.raw[j * circ.proof_len:(j + 1) * circ.proof_len] for j in range(B)]
+    bad = [j for j in range(B) if P[j] != ref["proofs"][j]]
+    assert not bad, "%d proofs differ from the C oracle's, first: %s" % (len(bad), bad[:8])
+    assert st["jobs"] == 2 and st["host_chains"] == 0, (st["jobs"], st["host_chains"])
 
 
 @pytest.fixture(scope="module")
