@@ -17,6 +17,7 @@ GADGETS_LIB_PATH = os.path.join(_HERE, "csrc", "libbpr1cs_gadgets.so")
 POSEIDON_PARAMS_PATH = os.path.join(_HERE, "data", "poseidon_params_ristretto.bin")
 
 VAR_COMMITTED, VAR_MUL_LEFT, VAR_MUL_RIGHT, VAR_MUL_OUT, VAR_ONE = 0, 1, 2, 3, 4
+VAR_PUBLIC = 5   # public input k of the proof at hand (include/bpr1cs.h "Public inputs"): its value rides in the calls' `publics`
 W_LC, W_INV_LEFT, W_BIT, W_NOTBIT = 0, 1, 2, 3
 
 ERRORS = {0: "OK", -1: "InvalidGeneratorsLength", -2: "FormatError", -3: "VerificationError",
@@ -155,6 +156,17 @@ def _u32arr(xs):
     return (ctypes.c_uint32 * max(1, len(xs)))(*xs)
 
 
+def _tail(block, publics, circuit, batch):
+    """`values` / `commitments` of a call with the public inputs behind them (include/bpr1cs.h: the tail block, batch x p x 32 bytes,
+    proof-major); a circuit without public inputs takes none"""
+    p = getattr(circuit, "p", 0)
+    publics = publics or b""
+    if not isinstance(publics, (bytes, bytearray)):
+        publics = b"".join(_sc(x) for row in publics for x in (row if isinstance(row, (list, tuple)) else [row]))
+    assert len(publics) == batch * p * 32, "publics: %d bytes, the circuit takes %d x %d x 32" % (len(publics), batch, p)
+    return bytes(block) + bytes(publics) if p else block
+
+
 class Gens:
     """PedersenGens::default() + BulletproofGens::new(capacity, 1)."""
 
@@ -211,8 +223,9 @@ class Gens:
 class Circuit:
     """Flattened constraint system (+ optional device witness program).
 
-    constraints: list of rows, each a list of ((kind, index), coeff_int_or_bytes)
+    constraints: list of rows, each a list of ((kind, index), coeff_int_or_bytes); kind VAR_PUBLIC = public input `index`
     wops: optional list of (lkind, larg, rkind, rarg); lcs: list of term lists for W_LC operands.
+    .p: public inputs per proof (1 + the highest index used, as the library derives it; raw=: scanned from the variable list).
     """
 
     def __init__(self, n, m, constraints, wops=None, lcs=None, lib=None, raw=None):
@@ -229,6 +242,9 @@ class Circuit:
                 row_off.append(len(tvar))
             q = len(constraints)
         self.q = q
+        pub = [v & 0x0fffffff for v in tvar if v >> 28 == VAR_PUBLIC]
+        pub += [idx for terms in (lcs or []) if wops is not None for (kind, idx), _ in terms if kind == VAR_PUBLIC]
+        self.p = 1 + max(pub) if pub else 0
         d = _CircuitDesc()
         d.n, d.q, d.m = n, q, m
         self._keep = [_u32arr(row_off), _u32arr(tvar), bytes(tcoef) or b"\0"]
@@ -261,8 +277,9 @@ class Circuit:
             pass
 
 
-def prove_batch(gens, circuit, label, values, v_blindings, rng_seeds, batch, wires=None):
+def prove_batch(gens, circuit, label, values, v_blindings, rng_seeds, batch, wires=None, publics=None):
     """-> (list of proof bytes, list of per-proof commitment lists).
+    publics: the public inputs of a circuit that has any - bytes batch*p*32 proof-major, or a list of per-proof lists.
 
     values / v_blindings: bytes batch*m*32 proof-major; rng_seeds: bytes batch*32;
     wires: None (device witness program) or bytes batch*3*n*32 (a_L|a_R|a_O per proof).
@@ -274,6 +291,7 @@ def prove_batch(gens, circuit, label, values, v_blindings, rng_seeds, batch, wir
         assert len(wires) == batch * 3 * circuit.n * 32
     proofs = ctypes.create_string_buffer(batch * plen)
     comms = ctypes.create_string_buffer(max(1, batch * m * 32))
+    values = _tail(values, publics, circuit, batch)
     _chk(lib.bpr1cs_prove_batch(gens.h, circuit.h, label, len(label), values or b"\0", v_blindings or b"\0", rng_seeds,
                                 wires, batch, proofs, comms))
     praw, craw = proofs.raw, comms.raw  # .raw copies the whole buffer: take it once
@@ -292,7 +310,7 @@ def refusal(proof_bytes):
     return dict(gate=first(REFUSAL_OFF_GATE), row=first(REFUSAL_OFF_ROW), gates=w(REFUSAL_OFF_GATE_COUNT), rows=w(REFUSAL_OFF_ROW_COUNT))
 
 
-def verify_batch(gens, circuit, label, proofs, commitments, batch, seeds=None):
+def verify_batch(gens, circuit, label, proofs, commitments, batch, seeds=None, publics=None):
     """proofs: list of bytes or concatenated bytes; commitments: list of lists (each m x 32 bytes) or bytes.
     -> list of bool (Verifier::verify accepted).  seeds: batch*32 bytes for the verifier's TranscriptRng
     (default: fresh os.urandom, as upstream's thread_rng)."""
@@ -300,13 +318,15 @@ def verify_batch(gens, circuit, label, proofs, commitments, batch, seeds=None):
         seeds = os.urandom(32 * batch)
     pf = proofs if isinstance(proofs, (bytes, bytearray)) else b"".join(proofs)
     cm = commitments if isinstance(commitments, (bytes, bytearray)) else b"".join(b"".join(c) for c in commitments)
-    assert len(pf) == batch * circuit.proof_len and len(cm) == batch * circuit.m * 32
+    assert len(cm) == batch * circuit.m * 32
+    cm = _tail(cm, publics, circuit, batch)   # public inputs of the proofs (bytes batch*p*32 or per-proof lists): behind the points
+    assert len(pf) == batch * circuit.proof_len
     ok = (ctypes.c_int * batch)()
     _chk(gens.lib.bpr1cs_verify_batch(gens.h, circuit.h, label, len(label), pf, cm or b"\0", seeds, batch, ok))
     return [bool(x) for x in ok]
 
 
-def verify_batch_combined(gens, circuit, label, proofs, commitments, batch, batch_seed=None, index_base=0, seeds=None):
+def verify_batch_combined(gens, circuit, label, proofs, commitments, batch, batch_seed=None, index_base=0, seeds=None, publics=None):
     """Cross-proof batched mega-check of this caller's `batch` proofs -> (partial point: 32 bytes, wellformed: bool).
     The whole job is accepted iff points_sum_is_identity(all callers' points) and all callers were well-formed.
     batch_seed / seeds default to fresh os.urandom (the weights must not be predictable, see include/bpr1cs.h)."""
@@ -316,7 +336,9 @@ def verify_batch_combined(gens, circuit, label, proofs, commitments, batch, batc
         seeds = os.urandom(32 * batch)
     pf = proofs if isinstance(proofs, (bytes, bytearray)) else b"".join(proofs)
     cm = commitments if isinstance(commitments, (bytes, bytearray)) else b"".join(b"".join(c) for c in commitments)
-    assert len(pf) == batch * circuit.proof_len and len(cm) == batch * circuit.m * 32 and len(batch_seed) == 32
+    assert len(cm) == batch * circuit.m * 32
+    cm = _tail(cm, publics, circuit, batch)   # public inputs of the proofs (bytes batch*p*32 or per-proof lists): behind the points
+    assert len(pf) == batch * circuit.proof_len and len(batch_seed) == 32
     out = ctypes.create_string_buffer(32)
     wf = ctypes.c_int()
     _chk(gens.lib.bpr1cs_verify_batch_combined(gens.h, circuit.h, label, len(label), pf, cm or b"\0", seeds, batch_seed, index_base, batch,
@@ -324,7 +346,7 @@ def verify_batch_combined(gens, circuit, label, proofs, commitments, batch, batc
     return out.raw, bool(wf.value)
 
 
-def verify_batch_scalars(gens, circuit, label, proofs, commitments, batch, batch_seed=None, index_base=0, seeds=None):
+def verify_batch_scalars(gens, circuit, label, proofs, commitments, batch, batch_seed=None, index_base=0, seeds=None, publics=None):
     """First half of the multi-GPU batched verifier -> (combined scalar vector: (2N+2)*32 bytes in base order
     B, B~, G.., H.., own-points sum: 32 bytes, wellformed)."""
     if batch_seed is None:
@@ -333,6 +355,7 @@ def verify_batch_scalars(gens, circuit, label, proofs, commitments, batch, batch
         seeds = os.urandom(32 * batch)
     pf = proofs if isinstance(proofs, (bytes, bytearray)) else b"".join(proofs)
     cm = commitments if isinstance(commitments, (bytes, bytearray)) else b"".join(b"".join(c) for c in commitments)
+    cm = _tail(cm, publics, circuit, batch)   # public inputs of the proofs (bytes batch*p*32 or per-proof lists): behind the points
     N = 1 << max(0, (circuit.n - 1).bit_length())
     out = ctypes.create_string_buffer(32 * (2 * N + 2))
     own = ctypes.create_string_buffer(32)
@@ -372,7 +395,7 @@ class Comm:
             pass
 
 
-def verify_batch_sharded(gens, circuit, label, proofs, commitments, batch, comm=None, batch_seed=None, index_base=0, seeds=None):
+def verify_batch_sharded(gens, circuit, label, proofs, commitments, batch, comm=None, batch_seed=None, index_base=0, seeds=None, publics=None):
     """The multi-GPU batched verifier in one call per rank (bpr1cs_verify_batch_sharded: RCCL all_gathers inside the library)
     -> True / False, the same on every rank.  comm = None: a job of one rank."""
     if batch_seed is None:
@@ -381,6 +404,7 @@ def verify_batch_sharded(gens, circuit, label, proofs, commitments, batch, comm=
         seeds = os.urandom(32 * batch)
     pf = proofs if isinstance(proofs, (bytes, bytearray)) else b"".join(proofs)
     cm = commitments if isinstance(commitments, (bytes, bytearray)) else b"".join(b"".join(c) for c in commitments)
+    cm = _tail(cm, publics, circuit, batch)   # public inputs of the proofs (bytes batch*p*32 or per-proof lists): behind the points
     ok = ctypes.c_int()
     _chk(gens.lib.bpr1cs_verify_batch_sharded(gens.h, circuit.h, label, len(label), pf, cm or b"\0", seeds, batch_seed, index_base, batch,
                                               comm.h if comm is not None else None, ctypes.byref(ok)))
@@ -514,8 +538,9 @@ def points_sum_is_identity(points, lib=None):
 class ProveJob:
     """An in-flight bpr1cs_prove_batch_begin; .finish() -> (proofs, commitments)."""
 
-    def __init__(self, gens, circuit, label, values, v_blindings, rng_seeds, batch, wires=None):
+    def __init__(self, gens, circuit, label, values, v_blindings, rng_seeds, batch, wires=None, publics=None):
         self.lib, self.batch, self.m, self.plen = gens.lib, batch, circuit.m, circuit.proof_len
+        values = _tail(values, publics, circuit, batch)
         h = ctypes.c_void_p()
         _chk(self.lib.bpr1cs_prove_batch_begin(gens.h, circuit.h, label, len(label), values or b"\0", v_blindings or b"\0", rng_seeds,
                                                wires, batch, ctypes.byref(h)))
@@ -544,7 +569,7 @@ def last_prove_stats(lib=None):
                 refused=st.refused)
 
 
-def prove_batch_transcripts(gens, circuit, transcripts, values, v_blindings, rng_seeds, batch, wires=None):
+def prove_batch_transcripts(gens, circuit, transcripts, values, v_blindings, rng_seeds, batch, wires=None, publics=None):
     """bpr1cs_prove_batch_transcripts: `transcripts` = one Transcript (every proof starts from a copy) or `batch` of them (each is
     advanced to the state upstream's `&mut transcript` has after prove()) -> (proofs, commitments) as prove_batch"""
     lib = gens.lib
@@ -553,6 +578,7 @@ def prove_batch_transcripts(gens, circuit, transcripts, values, v_blindings, rng
     m, plen = circuit.m, circuit.proof_len
     proofs = ctypes.create_string_buffer(batch * plen)
     comms = ctypes.create_string_buffer(max(1, batch * m * 32))
+    values = _tail(values, publics, circuit, batch)
     _chk(lib.bpr1cs_prove_batch_transcripts(gens.h, circuit.h, arr, len(ts), values or b"\0", v_blindings or b"\0", rng_seeds, wires, batch, proofs, comms))
     praw, craw = proofs.raw, comms.raw
     return ([praw[i * plen:(i + 1) * plen] for i in range(batch)],
@@ -568,10 +594,11 @@ def output_buffers(circuit, batch):
     return bufs
 
 
-def prove_batch_raw(gens, circuit, label, values, v_blindings, rng_seeds, batch, out=None):
+def prove_batch_raw(gens, circuit, label, values, v_blindings, rng_seeds, batch, out=None, publics=None):
     """ONE bpr1cs_prove_batch call over any batch (the library cuts it into device jobs) -> (proof bytes, commitment bytes), unsplit.
     out: (proofs, commitments) from output_buffers() - filled in place and returned as they are (no copy)"""
     m, plen = circuit.m, circuit.proof_len
+    values = _tail(values, publics, circuit, batch)
     if out is not None:
         pbuf, cbuf = out
         assert len(pbuf) >= batch * plen and len(cbuf) >= max(1, batch * m * 32)
@@ -636,7 +663,9 @@ def _sc(x):
 
 
 class CompiledGadget:
-    """A reference gadget compiled (shape only) into a device circuit + witness program."""
+    """A reference gadget compiled (shape only) into a device circuit + witness program.
+    The tree gadgets ("vsmt_4", "vsmt_2") compiled WITHOUT sparams take the root as public input 0 of every proof (.p == 1): one
+    circuit then proves and verifies memberships in different trees, `publics` = the roots."""
 
     def __init__(self, name, iparams=(), sparams=(), lib=None, glib=None):
         self.lib = lib or load_library()
@@ -649,6 +678,7 @@ class CompiledGadget:
                                              ctypes.byref(h), ctypes.byref(n), ctypes.byref(q), ctypes.byref(m), ctypes.byref(hw)))
         self.h, self.n, self.q, self.m, self.has_witness_program = h, n.value, q.value, m.value, bool(hw.value)
         self.proof_len = self.lib.bpr1cs_proof_len(h)
+        self.p = 1 if name in ("vsmt_4", "vsmt_2") and len(sparams) == 0 else 0   # (host/frontend.cpp run_gadget: the root as Variable::Public(0))
 
     def close(self):
         if self.h:

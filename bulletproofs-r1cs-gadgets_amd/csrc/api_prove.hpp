@@ -198,7 +198,7 @@ static void enqueue_witness_check(const bpr1cs_circuit* c, const sc* W, const sc
     const uint32_t nchunks = (uint32_t)c->h_row_chunk.size() - 1, per_launch = 0xffffffffu / Bpad;   // (a grid holds 2^32 - 1 threads)
     for (uint32_t c0 = 0; c0 < nchunks; c0 += per_launch)
         launch((uint64_t)std::min(per_launch, nchunks - c0) * Bpad,
-               K_check_rows{c->row_chunk.p, c->row_off.p, c->row_slot.p, c->row_coeff.p, W, v_m, res, B, Bpad, 3 * c->n, c->m, c0}, s);
+               K_check_rows{c->row_chunk.p, c->row_off.p, c->row_slot.p, c->row_coeff.p, W, v_m, res, B, Bpad, 3 * c->n, c->m + c->p, c0}, s);   // (value rows: committed, then public)
 }
 
 // One device job.  `init`: the transcripts the proofs start from - n_init = 1 (every proof starts from a copy of init[0]: what
@@ -206,20 +206,27 @@ static void enqueue_witness_check(const bpr1cs_circuit* c, const sc* W, const sc
 static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const strobe* init, size_t n_init, bool want_tr,
                            const uint8_t* values, const uint8_t* v_blindings, const uint8_t* rng_seeds,
                            const uint8_t* wires, size_t batch, bpr1cs_job** job_out, const uint8_t* ext_draws = nullptr, int auto_share = 0,
-                           bool first_of_call = false) {
+                           bool first_of_call = false, const uint8_t* publics = nullptr) {
+    // publics: this job's part of the public block - batch x p x 32, proof-major; nullptr = the block lies behind the job's own
+    // committed values (the caller handed in `values` of exactly this batch: bpr1cs_prove_batch_begin)
     // ext_draws (bpr1cs_prove_batch_draws): the caller has appended Prover::new's and commit's transcript messages and "m" itself - `init` holds
     // one transcript per proof in that state - and has run the proof's TranscriptRng: batch x (2n + 8) raw 64-byte draws
     if (!g || !c || !init || (!rng_seeds && !ext_draws) || !job_out || batch == 0 || (n_init != 1 && n_init != batch)) return BPR1CS_ERR_INVALID_ARGUMENT;
     if (ext_draws && n_init != batch) return BPR1CS_ERR_INVALID_ARGUMENT;
     if (c->m && (!values || !v_blindings)) return BPR1CS_ERR_INVALID_ARGUMENT;
+    if (c->p && !publics) {
+        if (!values) return BPR1CS_ERR_INVALID_ARGUMENT;
+        publics = values + batch * (size_t)c->m * 32;
+    }
     if (!have_device()) return BPR1CS_ERR_NO_DEVICE;
     if (g->cap < c->N) return BPR1CS_ERR_INVALID_GENERATORS_LENGTH;
     if (!wires && !c->has_program) return BPR1CS_ERR_MISSING_ASSIGNMENT;
     // the largest grid of a JOB must fit 2^32 threads (N = 32768: 26 000 proofs; bpr1cs_prove_batch cuts larger batches into jobs)
-    if (batch > (1u << 20) || ((uint64_t)4 * c->N + 3ull * c->n + c->m + 64) * batch > 0xffffffffull) return BPR1CS_ERR_INVALID_ARGUMENT;
+    if (batch > (1u << 20) || ((uint64_t)4 * c->N + 3ull * c->n + c->m + c->p + 64) * batch > 0xffffffffull) return BPR1CS_ERR_INVALID_ARGUMENT;
     // Scalar inputs are canonical encodings (Scalar::to_bytes); anything else is refused here
     if (c->m && (!host_scalars_canonical(values, batch * c->m) || !host_scalars_canonical(v_blindings, batch * c->m))) return BPR1CS_ERR_INVALID_ARGUMENT;
     if (wires && !host_scalars_canonical(wires, batch * 3 * (size_t)c->n)) return BPR1CS_ERR_INVALID_ARGUMENT;
+    if (c->p && !host_scalars_canonical(publics, batch * c->p)) return BPR1CS_ERR_INVALID_ARGUMENT;
     bpr1cs_job* job = nullptr;
     struct Scope {  // every buffer released while enqueuing stays alive until the job has drained
         std::vector<void*>* prev;
@@ -251,7 +258,7 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     // the handle's options, read once per job
     const int o_team = g->opts.witness_team.load(), o_tail = g->opts.tail_rounds.load();
     const bool o_check = g->opts.check_witness.load() != 0;
-    const uint32_t B = (uint32_t)batch, n = c->n, m = c->m, N = c->N, lgN = c->lgN;
+    const uint32_t B = (uint32_t)batch, n = c->n, m = c->m, N = c->N, lgN = c->lgN, np = c->p;
     const int o_unfold = (int)eff_unfold(g->opts, B, lgN);
     const uint32_t baseG = 2, baseH = 2 + g->cap;
     dev_stream_t st = job->st;
@@ -270,8 +277,9 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     // everything the caller hands over but the wires in ONE pinned block and ONE copy: committed values and blindings (element-major
     // [m][B]), the outside randomness, the transcripts the proofs start from.  (Four synchronous copies of a few hundred bytes each were
     // 0.1 ms in front of a 64-bit bound check's 3 ms.)
-    const size_t vb = (size_t)m * B * sizeof(sc), sb = (size_t)B * 32, ib = n_init * sizeof(strobe);
-    job->h_in_bytes = 2 * vb + sb + ib;
+    // (public inputs, when the circuit has any: element-major [p][B] like the values, at the end of the block)
+    const size_t vb = (size_t)m * B * sizeof(sc), sb = (size_t)B * 32, ib = n_init * sizeof(strobe), ub = (size_t)np * B * sizeof(sc);
+    job->h_in_bytes = 2 * vb + sb + ib + ub;
     job->h_in = (uint8_t*)host_stage_alloc(job->h_in_bytes);
     {
         sc* hv = (sc*)job->h_in;
@@ -283,6 +291,9 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
             }
         if (rng_seeds) memcpy(job->h_in + 2 * vb, rng_seeds, sb); else memset(job->h_in + 2 * vb, 0, sb);
         memcpy(job->h_in + 2 * vb + sb, init, ib);
+        sc* hu = (sc*)(job->h_in + 2 * vb + sb + ib);
+        for (size_t b = 0; b < B; b++)
+            for (size_t k = 0; k < np; k++) hu[k * B + b] = sc_load_raw(publics + (b * np + k) * 32);
     }
     DevBuf<uint8_t> d_in(job->h_in_bytes);
     dev_h2d_async(d_in.p, job->h_in, job->h_in_bytes, sl);
@@ -290,9 +301,11 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     sc* vbl_raw = (sc*)d_in.p + (size_t)m * B;
     uint8_t* d_seeds = d_in.p + 2 * vb;
     strobe* d_init = (strobe*)(d_in.p + 2 * vb + sb);
-    DevBuf<sc> v_m((size_t)m * B), vbl_m((size_t)m * B);
+    // v_m: the committed values and, in rows m .. m+p-1, the public inputs - the value rows the witness program and the witness check read
+    DevBuf<sc> v_m((size_t)(m + np) * B), vbl_m((size_t)m * B);
     const uint32_t init_stride = n_init == 1 ? 0u : 1u;
     launch((uint64_t)m * B, K_load_inputs{v_raw, vbl_raw, v_m.p, vbl_m.p}, sl);
+    if (np) launch((uint64_t)np * B, K_load_wires{(const sc*)(d_in.p + 2 * vb + sb + ib), v_m.p + (size_t)m * B}, sl);
 
     DBG_JOB("begin: inputs uploaded");
     // ---- P1: V commitments, transcript, RNG stream
@@ -752,7 +765,7 @@ static uint32_t auto_job_proofs(const bpr1cs_gens* g, const bpr1cs_circuit* c, b
     const size_t Mr = N >> r, nfl = c->h_slot_chunk.empty() ? 0 : c->h_slot_chunk[3 * n + m];
     const size_t tail_m = std::min<size_t>(N, 128);
     const size_t front_shared = 160 * n + 64 * (2 * n + 7);   // W and the raw TranscriptRng output: ONE copy for the jobs in flight
-    const size_t front = 200 * m + 4 * 32 * (size_t)c->px_stride + 512 + c->lgN * 128 +
+    const size_t front = 200 * m + 64 * (size_t)c->p + 4 * 32 * (size_t)c->px_stride + 512 + c->lgN * 128 +   // (public inputs: raw and Montgomery form)
                          tail_m * (2 * 32 + 2 * sizeof(ge)) + (tail_m / 2) * (4 * VB_MULT * sizeof(ge_cached) + 4 * VB_WORDS * 4) + 2 * VB_WINDOWS * 5 * sizeof(ge);
     const size_t others = 32 * (3 * n + m + nfl) + 64 * N, vt = r < c->lgN ? (size_t)VB_MULT * 4 * std::max<size_t>(1, Mr / 2) * sizeof(ge_cached) : 0;
     const size_t back = std::max(others, vt) + 64 * N + 2 * VB_WINDOWS * sizeof(ge) + 30000;   // (folded generators, digits, window sums: inside the dead rows of l / r)
@@ -769,7 +782,7 @@ static uint32_t auto_job_proofs(const bpr1cs_gens* g, const bpr1cs_circuit* c, b
     }
     const size_t avail = dev_free_memory() + g->arena.bytes() + g->front[0].bytes() + g->front[1].bytes() + g->shared_front.bytes();
     const size_t reserve = (size_t)4 << 30;   // what must stay free at the peak (the HIP runtime's own needs, another handle's small jobs)
-    const uint64_t grid_per_proof = (uint64_t)4 * c->N + 3ull * c->n + c->m + 64;
+    const uint64_t grid_per_proof = (uint64_t)4 * c->N + 3ull * c->n + c->m + c->p + 64;
     // (small circuits: measured 104 k / 116 k / 126 k / 128 k proofs/s at 4096 / 8192 / 16384 / 32768 proofs per job for the 2:1 Poseidon
     // preimage circuit, 62.8 k / 69.0 k / 71.6 k / 70.5 k for MiMC + set membership)
     if (why) { why->avail = avail; why->per_proof = (uint64_t)front * in_flight + front_shared + back; why->fixed = fixed + reserve; }
@@ -795,7 +808,7 @@ static int prove_batch_impl(const bpr1cs_gens* g, const bpr1cs_circuit* c, const
     bpr1cs_prove_stats acc{};
     const int depth = g->opts.jobs_in_flight.load() == 1 ? 1 : 2;
     size_t J = (size_t)g->opts.job_proofs.load();
-    const uint64_t grid_per_proof = (uint64_t)4 * c->N + 3ull * c->n + c->m + 64;
+    const uint64_t grid_per_proof = (uint64_t)4 * c->N + 3ull * c->n + c->m + c->p + 64;
     const size_t grid_max = (size_t)std::min<uint64_t>(0xffffffffull / grid_per_proof, 1u << 20);
     if (grid_max == 0) return BPR1CS_ERR_INVALID_ARGUMENT;
     const bool automatic = J == 0;
@@ -825,6 +838,9 @@ static int prove_batch_impl(const bpr1cs_gens* g, const bpr1cs_circuit* c, const
     if (automatic) J = known ? known : remember(auto_job_proofs(g, c, wires == nullptr, depth, &why));
     J = std::min(J, grid_max);
     const size_t m = c->m, plen = bpr1cs_proof_len(c), wn = 3 * (size_t)c->n;
+    // public inputs: the tail block of `values`, behind the committed values of the WHOLE batch; cut per job like them
+    if (c->p && !values) return BPR1CS_ERR_INVALID_ARGUMENT;
+    const uint8_t* publics = c->p ? values + batch * m * 32 : nullptr;
     struct Pending { bpr1cs_job* job; size_t first; };
     std::vector<Pending> fl;
     int rc = BPR1CS_OK;
@@ -876,7 +892,8 @@ static int prove_batch_impl(const bpr1cs_gens* g, const bpr1cs_circuit* c, const
         else e = prove_job_begin(g, c, n_init == 1 ? init : init + done, n_init == 1 ? 1 : take, tr_out != nullptr,
                                  values ? values + done * m * 32 : nullptr, v_blindings ? v_blindings + done * m * 32 : nullptr,
                                  rng_seeds ? rng_seeds + done * 32 : nullptr, wires ? wires + done * wn * 32 : nullptr, take, &job,
-                                 ext_draws ? ext_draws + done * (2 * (size_t)c->n + 8) * 64 : nullptr, auto_share(take), fl.empty());
+                                 ext_draws ? ext_draws + done * (2 * (size_t)c->n + 8) * 64 : nullptr, auto_share(take), fl.empty(),
+                                 publics ? publics + done * (size_t)c->p * 32 : nullptr);
         if (e == BPR1CS_ERR_OUT_OF_MEMORY && (take > 64 || !retried)) {
             // out of memory: let the jobs in flight finish and hand the scratch back (arenas sized for the smaller jobs of an
             // earlier call sit next to the blocks that replace them until their last user has drained) - then the same job once

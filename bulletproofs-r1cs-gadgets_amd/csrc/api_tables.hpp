@@ -186,9 +186,17 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
         for (uint32_t j = 0; j < d->q; j++)
             if (d->row_off[j + 1] < d->row_off[j]) return BPR1CS_ERR_INVALID_ARGUMENT;
     }
+    // public inputs (BPR1CS_VAR_PUBLIC): p = 1 + the highest index used by a constraint term or a linear combination.  p sizes the
+    // tail block of every later call, so only a term that USES its input may set it: a public term whose coefficient is 0 (mod l) is
+    // refused - it says nothing, and a description that holds one (a zeroed coefficient array, a kind written by mistake) would
+    // silently oblige every prove and verify call to carry values nothing reads
+    const uint32_t PUBLIC_MAX = 1u << 20;
+    uint32_t npub = 0;
+    auto public_term_ok = [&](uint32_t var, const uint8_t* coeff) { return (var >> 28) != VK_PUBLIC || !sc_is_zero(host_mont(coeff)); };
     auto var_ok = [&](uint32_t var, uint32_t wire_limit) {  // wire_limit: multipliers a reference may point at
         uint32_t kind = var >> 28, idx = var & 0x0fffffffu;
         if (kind == VK_ONE) return true;
+        if (kind == VK_PUBLIC) { if (idx >= PUBLIC_MAX) return false; npub = std::max(npub, idx + 1); return true; }
         if (kind == VK_COMMITTED) return idx < d->m;
         return kind <= VK_OUT && idx < wire_limit;
     };
@@ -198,6 +206,10 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
             if (d->lc_off[0] != 0) return BPR1CS_ERR_INVALID_ARGUMENT;
             for (uint32_t k = 0; k < d->n_lc; k++)
                 if (d->lc_off[k + 1] < d->lc_off[k]) return BPR1CS_ERR_INVALID_ARGUMENT;
+            // (every combination counts towards p, one that only a Poseidon annotation refers to as well)
+            for (uint32_t t = 0; t < d->lc_off[d->n_lc]; t++)
+                if ((d->lc_var[t] >> 28) == VK_PUBLIC && (!var_ok(d->lc_var[t], 0) || !public_term_ok(d->lc_var[t], d->lc_coeff + 32 * (size_t)t)))
+                    return BPR1CS_ERR_INVALID_ARGUMENT;
         }
         // a multiplier's operands may only read committed values, the constant, and wires of EARLIER multipliers
         // (the sequential program of K_witness / k_witness_team writes multiplier i after evaluating both operands)
@@ -216,6 +228,9 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
             if (!operand_ok(d->wops[i].lkind, d->wops[i].larg, i, false) || !operand_ok(d->wops[i].rkind, d->wops[i].rarg, i, true))
                 return BPR1CS_ERR_INVALID_ARGUMENT;
     }
+    for (uint32_t t = 0, nnz0 = d->q ? d->row_off[d->q] : 0; t < nnz0; t++)
+        if ((d->term_var[t] >> 28) == VK_PUBLIC && (!var_ok(d->term_var[t], 0) || !public_term_ok(d->term_var[t], d->term_coeff + 32 * (size_t)t)))
+            return BPR1CS_ERR_INVALID_ARGUMENT;
     // a description without a witness program that was built before (the per-proof circuit of a drop-in Prover / Verifier): the same object
     const bool cacheable = !d->wops;
     uint64_t cache_key = 0;
@@ -226,21 +241,23 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
     bpr1cs_circuit* c = nullptr;
     API_TRY
     c = new bpr1cs_circuit();
-    c->n = d->n; c->q = d->q; c->m = d->m;
+    c->n = d->n; c->q = d->q; c->m = d->m; c->p = npub;
     c->N = 1; c->lgN = 0;
     while (c->N < d->n) { c->N <<= 1; c->lgN++; }
     dev_stream_t s{};
     CallScope scope(s);
     const char* wm_env = getenv("BPR1CS_WITNESS_MACRO");   // diagnostic (include/bpr1cs.h, "Environment"): 0 = run every S-box op by op (one inversion each); same results
     const int witness_macro = !(wm_env && wm_env[0] == '0');
-    // CSR by row -> CSC by wire slot (LEFT i -> i, RIGHT -> n+i, OUT -> 2n+i, COMMITTED -> 3n+i, One -> 3n+m).
-    // The prover flattens slots [0, 3n+m) (it ignores constant terms); the verifier also needs slot 3n+m (w_c).
-    uint32_t nslots = 3 * d->n + d->m + 1;
+    // CSR by row -> CSC by wire slot (LEFT i -> i, RIGHT -> n+i, OUT -> 2n+i, COMMITTED -> 3n+i, PUBLIC k -> 3n+m+k, One -> 3n+m+p).
+    // The prover flattens slots [0, 3n+m) (it ignores constant terms, public inputs among them); the verifier also needs the p
+    // public columns and slot 3n+m+p (w_c).  (3n + m + p + 1 <= 3 * 2^24 + 2^21 < 2^26: the slot words of the row form keep their flag bits.)
+    uint32_t nslots = 3 * d->n + d->m + npub + 1;
     std::vector<uint32_t> cnt(nslots + 1, 0);
     uint32_t nnz = d->q ? d->row_off[d->q] : 0;
     auto slot_of = [&](uint32_t var, uint32_t& slot) -> int {
         uint32_t kind = var >> 28, idx = var & 0x0fffffffu;
-        if (kind == VK_ONE) { slot = 3 * d->n + d->m; return 1; }
+        if (kind == VK_ONE) { slot = 3 * d->n + d->m + npub; return 1; }
+        if (kind == VK_PUBLIC) { if (idx >= npub) return -1; slot = 3 * d->n + d->m + idx; return 1; }
         if (kind == VK_COMMITTED) { if (idx >= d->m) return -1; slot = 3 * d->n + idx; return 1; }
         if (kind > VK_OUT || idx >= d->n) return -1;
         slot = (kind - 1) * d->n + idx;
@@ -292,7 +309,7 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
             (void)slot_of(d->term_var[t], slot);   // (validated by the counting loop above)
             const sc co = host_mont(d->term_coeff + 32 * (size_t)t);
             c->h_row_coeff[t] = co;
-            // (slot <= 3n + m < 2^26: the two top bits carry the +-1 flags, as in ent_row)
+            // (slot <= 3n + m + p < 2^26: the two top bits carry the +-1 flags, as in ent_row)
             c->h_row_slot[t] = slot | (memcmp(&co, &one_m, sizeof(sc)) == 0 ? 0x80000000u : 0u) | (memcmp(&co, &minus_one_m, sizeof(sc)) == 0 ? 0x40000000u : 0u);
         }
         // chunks of consecutive whole rows, closed when their entries reach CHECK_CHUNK: a row is never split, a row of CHECK_CHUNK
@@ -313,6 +330,9 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
         for (uint32_t i = 0; i < d->n; i++) ops[i] = WOp{d->wops[i].lkind, d->wops[i].larg, d->wops[i].rkind, d->wops[i].rarg};
         uint32_t nt = d->n_lc ? d->lc_off[d->n_lc] : 0;
         std::vector<uint32_t> lo(d->lc_off, d->lc_off + d->n_lc + 1), lv(d->lc_var, d->lc_var + nt);
+        // a public input is a read of value row m + k: the prove job lays the public block behind the committed values (v_m), and
+        // K_witness / k_witness_team read it as they read a committed value
+        auto as_row = [&](uint32_t var) { return (var >> 28) == VK_PUBLIC ? (VK_COMMITTED << 28) | (d->m + (var & 0x0fffffffu)) : var; };
         std::vector<sc> lcf(nt);
         for (uint32_t t = 0; t < nt; t++) lcf[t] = host_mont(d->lc_coeff + 32 * (size_t)t);
         // specialise trivial linear combinations: {1 * var} -> WK_VAR, {} -> WK_ZERO
@@ -321,7 +341,7 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
             if (kind != WK_LC || arg >= d->n_lc) return;
             uint32_t t0 = lo[arg], t1 = lo[arg + 1];
             if (t1 == t0) { kind = WK_ZERO; arg = 0; return; }
-            if (t1 == t0 + 1 && memcmp(&lcf[t0], &one, sizeof(sc)) == 0) { kind = WK_VAR; arg = lv[t0]; }
+            if (t1 == t0 + 1 && memcmp(&lcf[t0], &one, sizeof(sc)) == 0) { kind = WK_VAR; arg = as_row(lv[t0]); }
         };
         // Poseidon annotations: validate, then route the S-box multipliers to the jointly evaluated values.
         // Anything unexpected leaves the plain program in place (it is complete on its own).
@@ -407,6 +427,7 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
         for (auto& op : ops) { special(op.lkind, op.larg); special(op.rkind, op.rarg); }
         upload(c->wops, ops, s);
         upload(c->lc_off, lo, s);
+        for (auto& var : lv) var = as_row(var);   // (after the last check of the caller's own numbering)
         upload(c->lc_var, lv, s);
         upload(c->lc_coeff, lcf, s);
     }

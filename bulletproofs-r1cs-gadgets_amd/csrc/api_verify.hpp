@@ -5,6 +5,8 @@
 static const uint32_t VERIFY_HOST_TRANSCRIPT_MAX_PROOFS = 8;
 struct VerifyCtx {  // device state shared by the per-proof and the cross-proof verifier
     uint32_t B, n, m, N, lgN, H, P;
+    uint32_t p = 0;                 // public inputs per proof
+    const uint8_t* d_pub = nullptr; // [B][p][32] canonical bytes: the tail block of `commitments`, behind the points in d_vc
     size_t plen;
     DevBuf<uint8_t> d_pf, d_vc, d_seed, d_label, bind;
     DevBuf<sc> chal, uk, plo, phi, wvec, gh, dpart, delta, bsc;
@@ -12,20 +14,22 @@ struct VerifyCtx {  // device state shared by the per-proof and the cross-proof 
 };
 static int verify_args_ok(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, const uint8_t* proofs, const uint8_t* commitments, size_t batch) {
     if (!g || !c || !label || !proofs || batch == 0 || batch > (1u << 20)) return BPR1CS_ERR_INVALID_ARGUMENT;
-    if (c->m && !commitments) return BPR1CS_ERR_INVALID_ARGUMENT;
+    if ((c->m || c->p) && !commitments) return BPR1CS_ERR_INVALID_ARGUMENT;
     if (!have_device()) return BPR1CS_ERR_NO_DEVICE;
     if (g->cap < c->N) return BPR1CS_ERR_INVALID_GENERATORS_LENGTH;
-    if (((uint64_t)4 * c->N + 3ull * c->n + c->m + 64) * batch > 0xffffffffull) return BPR1CS_ERR_INVALID_ARGUMENT;
+    if (((uint64_t)4 * c->N + 3ull * c->n + c->m + c->p + 64) * batch > 0xffffffffull) return BPR1CS_ERR_INVALID_ARGUMENT;
     return BPR1CS_OK;
 }
 // transcript replay, flattened constraints, mega-check scalars of the shared bases: gh = g_i | h_i (canonical), bsc (Montgomery)
 static void verify_front(VerifyCtx& v, const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len, const uint8_t* proofs,
                          const uint8_t* commitments, const uint8_t* verifier_rng_seeds, size_t batch, bool want_bind, dev_stream_t st) {
     const uint32_t B = v.B = (uint32_t)batch, n = v.n = c->n, m = v.m = c->m, N = v.N = c->N, lgN = v.lgN = c->lgN;
+    const uint32_t p = v.p = c->p;
     v.plen = bpr1cs_proof_len(c);
-    v.d_pf.alloc((size_t)B * v.plen); v.d_vc.alloc((size_t)B * m * 32 + 1); v.d_seed.alloc((size_t)B * 32); v.d_label.alloc(label_len ? label_len : 1);
+    v.d_pf.alloc((size_t)B * v.plen); v.d_vc.alloc((size_t)B * (m + p) * 32 + 1); v.d_seed.alloc((size_t)B * 32); v.d_label.alloc(label_len ? label_len : 1);
     dev_h2d(v.d_pf.p, proofs, (size_t)B * v.plen, st);
-    if (m) dev_h2d(v.d_vc.p, commitments, (size_t)B * m * 32, st);
+    if (m + p) dev_h2d(v.d_vc.p, commitments, (size_t)B * (m + p) * 32, st);   // the points and, behind them, the public inputs: one block
+    v.d_pub = v.d_vc.p + (size_t)B * m * 32;
     if (verifier_rng_seeds) dev_h2d(v.d_seed.p, verifier_rng_seeds, (size_t)B * 32, st);
     else dev_zero(v.d_seed.p, (size_t)B * 32, st);
     if (label_len) dev_h2d(v.d_label.p, label, label_len, st);
@@ -59,7 +63,7 @@ static void verify_front(VerifyCtx& v, const bpr1cs_gens* g, const bpr1cs_circui
     v.H = (maxe >> 8) + 1;
     v.plo.alloc((size_t)3 * 256 * B); v.phi.alloc((size_t)3 * v.H * B);
     launch_pow_tables(K_pow_tables{v.chal.p, v.plo.p, v.phi.p, B, v.H}, B, st);
-    const uint32_t nslots = 3 * n + m + 1;
+    const uint32_t nslots = 3 * n + m + p + 1;
     v.wvec.alloc((size_t)nslots * B);
     run_flatten(c, nslots, v.plo.p, v.phi.p, v.wvec.p, B, v.H, st);
     v.gh.alloc((size_t)2 * N * B); v.dpart.alloc((size_t)N * B); v.delta.alloc(B); v.bsc.alloc((size_t)2 * B);
@@ -71,7 +75,18 @@ static void verify_front(VerifyCtx& v, const bpr1cs_gens* g, const bpr1cs_circui
     } else {
         launch_sum_partials(B, K_sum_partials{v.dpart.p, v.delta.p, B, N}, st);
     }
-    launch(B, K_verify_bscalars{v.chal.p, v.wvec.p + (size_t)(3 * n + m) * B, v.delta.p, v.bsc.p, B}, st);
+    sc* wc = v.wvec.p + (size_t)(3 * n + m + p) * B;
+    if (p) {   // w_c += sum_k (column of public input k) x p_k; a non-canonical public input makes its proof malformed
+        K_verify_public kpub{v.wvec.p + (size_t)(3 * n + m) * B, v.d_pub, wc, v.fail.p, B, p};
+#if !defined(BPR1CS_HOSTSIM)
+        if (B <= FINISH_WAVE_MAX_PROOFS) {
+            hipLaunchKernelGGL(k_verify_public_wave, dim3(B), dim3(64), 0, st, kpub);
+            HIPCHK(hipGetLastError());
+        } else
+#endif
+        launch(B, kpub, st);
+    }
+    launch(B, K_verify_bscalars{v.chal.p, wc, v.delta.p, v.bsc.p, B}, st);
     v.P = 8 + m + 2 * lgN;
 }
 
@@ -151,7 +166,7 @@ static void verify_weights(CombinedCtx& k, VerifyCtx& v, const uint8_t* batch_se
     dev_h2d(k.d_bseed.p, batch_seed, 32, st);
     const uint32_t leaves = (B + BATCH_LEAF - 1) / BATCH_LEAF;
     DevBuf<uint8_t> leaf((size_t)leaves * 32);
-    launch(leaves, K_batch_leaf{v.bind.p, leaf.p, B}, st);
+    launch(leaves, K_batch_leaf{v.bind.p, leaf.p, B, v.d_pub, v.p}, st);
     launch(1, K_batch_digest{k.d_bseed.p, leaf.p, k.digest.p, index_base, B}, st);
     launch(B, K_batch_weights{k.digest.p, k.rho.p, index_base}, st);
 }
@@ -329,12 +344,14 @@ static int verify_batch_grouped_once(const bpr1cs_gens* g, const bpr1cs_circuit*
     }
     if (redo.empty()) return BPR1CS_OK;
     // the inputs are host memory: the sub-batch is gathered here and takes the per-proof path as a batch of its own
-    const size_t plen = bpr1cs_proof_len(c), clen = (size_t)c->m * 32;
-    std::vector<uint8_t> sp(redo.size() * plen), sc_(redo.size() * clen + 1), ss(verifier_rng_seeds ? redo.size() * 32 : 0);
+    const size_t plen = bpr1cs_proof_len(c), clen = (size_t)c->m * 32, ulen = (size_t)c->p * 32;   // (public inputs: the tail block of both arrays)
+    const uint8_t* pub = commitments ? commitments + batch * clen : nullptr;
+    std::vector<uint8_t> sp(redo.size() * plen), sc_(redo.size() * (clen + ulen) + 1), ss(verifier_rng_seeds ? redo.size() * 32 : 0);
     std::vector<int> sok(redo.size(), 0);
     for (size_t i = 0; i < redo.size(); i++) {
         memcpy(sp.data() + i * plen, proofs + redo[i] * plen, plen);
         if (clen) memcpy(sc_.data() + i * clen, commitments + redo[i] * clen, clen);
+        if (ulen) memcpy(sc_.data() + redo.size() * clen + i * ulen, pub + redo[i] * ulen, ulen);
         if (verifier_rng_seeds) memcpy(ss.data() + i * 32, verifier_rng_seeds + redo[i] * 32, 32);
     }
     rc = verify_batch_once(g, c, label, label_len, sp.data(), sc_.data(), verifier_rng_seeds ? ss.data() : nullptr, redo.size(), sok.data());

@@ -57,6 +57,8 @@ HD inline int tab_digit(const sc& s, uint32_t k, int& carry, const TabCfg& tc) {
 #define VK_RIGHT 2u
 #define VK_OUT 3u
 #define VK_ONE 4u
+#define VK_PUBLIC 5u  // public input #index of the proof at hand (constraint terms and linear combinations; bpr1cs_circuit_create turns it
+                      // into value row m + index of the witness program and into slot 3n + m + index of the flattening)
 
 // witness-program operand kinds
 #define WK_LC 0u        // evaluate linear combination #arg
@@ -1847,6 +1849,29 @@ struct K_verify_bscalars {  // gid = b
         out[(size_t)B + b] = cBb;
     }
 };
+// Public inputs (BPR1CS_VAR_PUBLIC): canonical bytes [B][p][32] as the caller lays them out -> fail[b] for a proof that holds a
+// non-canonical one, and w_c[b] += sum_k wpub[k][b] * p[b][k] - the flattened columns of the public slots, negated by K_flatten like
+// the constant's own, times the values: from here on w_c is that of the circuit with coeff x p_k folded into its One coefficients.
+// A malformed proof's sum is left out (its verdict is 0 whatever its scalars are).
+HD inline sc public_term(const sc* wpub, const uint8_t* pub, uint32_t B, uint32_t p, uint32_t b, uint32_t k, int& bad) {
+    const uint8_t* v = pub + ((size_t)b * p + k) * 32;
+    if (!scalar_bytes_canonical(v)) { bad = 1; return sc_zero(); }
+    return sc_mul(wpub[(size_t)k * B + b], sc_to_mont(sc_load_raw(v)));
+}
+struct K_verify_public {  // gid = b
+    const sc* wpub;      // [p][B] slots 3n+m .. 3n+m+p-1 of the flattened constraints
+    const uint8_t* pub;  // [B][p][32]
+    sc* wc;              // [B] slot 3n+m+p
+    int* fail;           // [B]
+    uint32_t B, p;
+    HD void operator()(uint32_t b) const {
+        sc acc = sc_zero();
+        int bad = 0;
+        for (uint32_t k = 0; k < p; k++) acc = sc_add(acc, public_term(wpub, pub, B, p, b, k, bad));
+        if (bad) fail[b] = 1;
+        else wc[b] = sc_add(wc[b], acc);
+    }
+};
 // the proof's own points: decompress, multiply by their mega-check scalar
 struct K_verify_points {  // gid = p*B + b, p < 8 + m + 2 lgN
     const uint8_t* proofs;
@@ -1920,13 +1945,19 @@ struct K_batch_leaf {  // gid = leaf : leaf[gid] = challenge("leaf") of Merlin("
     const uint8_t* bind;  // [B][32]
     uint8_t* leaf;        // [ceil(B / 32)][32]
     uint32_t B;
+    // a circuit with public inputs: ("public", p_b,0 || ... || p_b,p-1) behind each proof's binding value (include/bpr1cs.h)
+    const uint8_t* pub = nullptr;  // [B][p][32]
+    uint32_t p = 0;
     HD void operator()(uint32_t g) const {
         strobe t;
         const char lab[] = "bpr1cs batch leaf";
         merlin_new(t, (const uint8_t*)lab, sizeof(lab) - 1);
         merlin_append_u64(t, "leaf", 4, g);
         uint32_t lo = g * BATCH_LEAF, hi = lo + BATCH_LEAF < B ? lo + BATCH_LEAF : B;
-        for (uint32_t b = lo; b < hi; b++) merlin_append(t, "proof", 5, bind + 32 * (size_t)b, 32);
+        for (uint32_t b = lo; b < hi; b++) {
+            merlin_append(t, "proof", 5, bind + 32 * (size_t)b, 32);
+            if (p) merlin_append(t, "public", 6, pub + (size_t)b * p * 32, p * 32);
+        }
         merlin_challenge_bytes(t, "leaf", 4, leaf + 32 * (size_t)g, 32);
     }
 };

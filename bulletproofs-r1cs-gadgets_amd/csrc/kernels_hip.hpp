@@ -202,6 +202,29 @@ __global__ void __launch_bounds__(64) k_dot_wave(const sc* x, const sc* y, sc* o
     if (lane == 0) out[b] = acc;
 }
 
+// K_verify_public for a batch of a few proofs: a wavefront per proof, the lanes take every 64th public input (the canonical test,
+// the conversion and the product of a term are public_term's, as in the functor) and a shuffle butterfly adds the 64 partial sums
+// and ORs their flags - as k_dot_wave; the sum mod l does not depend on the order.
+__global__ void __launch_bounds__(64) k_verify_public_wave(K_verify_public f) {
+    const uint32_t b = blockIdx.x, lane = threadIdx.x;
+    if (b >= f.B) return;   // (whole wavefront: blockIdx is uniform)
+    sc acc = sc_zero();
+    int bad = 0;
+    for (uint32_t k = lane; k < f.p; k += 64u) acc = sc_add(acc, public_term(f.wpub, f.pub, f.B, f.p, b, k, bad));
+#pragma unroll 1
+    for (int sft = 32; sft > 0; sft >>= 1) {
+        sc o;
+#pragma unroll
+        for (int i = 0; i < 8; i++) o.v[i] = (uint32_t)__shfl_xor((int)acc.v[i], sft, 64);
+        acc = sc_add(acc, o);
+        bad |= __shfl_xor(bad, sft, 64);
+    }
+    if (lane == 0) {
+        if (bad) f.fail[b] = 1;
+        else f.wc[b] = sc_add(f.wc[b], acc);
+    }
+}
+
 // K_commit_T for a job of a few proofs: a wavefront per T commitment (as k_commit_wave: table entries on 2 x windows lanes, butterfly,
 // lane 0 compresses) instead of a lane walking 2 x windows additions.
 __global__ void __launch_bounds__(64) k_commit_T_wave(K_commit_T f) {

@@ -153,7 +153,7 @@ void Verifier::verify(const R1CSProof& proof, const PedersenGens&, const Bulletp
 bpr1cs_circuit* CircuitCompiler::finish(uint32_t* n_out, uint32_t* q_out, uint32_t* m_out) {
     std::vector<uint32_t> row_off, tvar;
     std::vector<uint8_t> tcoeff;
-    export_csr(row_off, tvar, tcoeff);
+    export_csr(row_off, tvar, tcoeff, true);
     bpr1cs_circuit_desc d{};
     d.n = (uint32_t)num_vars; d.q = (uint32_t)constraints.size(); d.m = (uint32_t)V_.size();
     d.row_off = row_off.data(); d.term_var = tvar.data(); d.term_coeff = tcoeff.data();
@@ -369,17 +369,23 @@ static size_t run_gadget(const GadgetSpec& g, Harness& h) {
     // trees: optional third ip = S-box of the tree's Poseidon (1 / absent: Inverse as the reference hard-wires it,
     // gadget_vsmt_4.rs:301, gadget_vsmt_2.rs:203; 0: Cube)
     auto tree_sbox = [&]() { return (g.ip.size() > 2 && g.ip[2] == 0) ? SboxType::Cube : SboxType::Inverse; };
-    if (g.name == "vsmt_4") {  // src/gadget_vsmt_4.rs:363-440 ; ip = [levels, partial_rounds(, sbox)], sp = [root]
+    // a tree gadget COMPILED without `sp`: the root is public input 0 of every proof (Variable::Public, include/bpr1cs.h "Public
+    // inputs"); Prover and Verifier need sp = [root], as before
+    const Variable pub0 = Variable::Public(0);
+    const bool root_public = g.sp.empty() && dynamic_cast<CircuitCompiler*>(&h.cs) != nullptr;
+    const Variable* pub_root = root_public ? &pub0 : nullptr;
+    const Scalar no_root;
+    if (g.name == "vsmt_4") {  // src/gadget_vsmt_4.rs:363-440 ; ip = [levels, partial_rounds(, sbox)], sp = [root] (compiled: [] = public root)
         size_t levels = g.ip.at(0);
         PoseidonParams params(6, 4, 4, g.ip.at(1), g.blob, g.blob_len);
         auto leaf = AS(0), idx = AS(1);
         std::vector<AllocatedScalar> nodes;
         for (size_t i = 0; i < 3 * levels; i++) nodes.push_back(AS(2 + i));
         auto st = statics_from(2 + 3 * levels, 2);
-        vanilla_merkle_merkle_tree_4_verif_gadget(h.cs, levels, g.sp.at(0), leaf, idx, nodes, st, params, levels / 4, tree_sbox());
+        vanilla_merkle_merkle_tree_4_verif_gadget(h.cs, levels, root_public ? no_root : g.sp.at(0), leaf, idx, nodes, st, params, levels / 4, tree_sbox(), pub_root);
         return 4 + 3 * levels;
     }
-    if (g.name == "vsmt_2") {  // src/gadget_vsmt_2.rs:262-352 ; ip = [depth, partial_rounds(, sbox)], sp = [root]
+    if (g.name == "vsmt_2") {  // src/gadget_vsmt_2.rs:262-352 ; ip = [depth, partial_rounds(, sbox)], sp = [root] (compiled: [] = public root)
         size_t depth = g.ip.at(0);
         PoseidonParams params(6, 4, 4, g.ip.at(1), g.blob, g.blob_len);
         auto leaf = AS(0);
@@ -387,7 +393,7 @@ static size_t run_gadget(const GadgetSpec& g, Harness& h) {
         for (size_t i = 0; i < depth; i++) bits.push_back(AS(1 + i));
         for (size_t i = 0; i < depth; i++) nodes.push_back(AS(1 + depth + i));
         auto st = statics_from(1 + 2 * depth, 4);
-        vanilla_merkle_merkle_tree_verif_gadget(h.cs, depth, g.sp.at(0), leaf, bits, nodes, st, params, tree_sbox());
+        vanilla_merkle_merkle_tree_verif_gadget(h.cs, depth, root_public ? no_root : g.sp.at(0), leaf, bits, nodes, st, params, tree_sbox(), pub_root);
         return 5 + 2 * depth;
     }
     throw R1CSError::GadgetError("unknown gadget " + g.name);

@@ -878,7 +878,10 @@ public:
 inline void vanilla_merkle_merkle_tree_4_verif_gadget(ConstraintSystem& cs, size_t depth, const Scalar& root, const AllocatedScalar& leaf_val,
                                                       const AllocatedScalar& leaf_index, std::vector<AllocatedScalar> proof_nodes,
                                                       const std::vector<AllocatedScalar>& statics_, const PoseidonParams& poseidon_params,
-                                                      size_t leaf_index_bytes, SboxType sbox_type = SboxType::Inverse) {
+                                                      size_t leaf_index_bytes, SboxType sbox_type = SboxType::Inverse,
+                                                      const Variable* public_root = nullptr) {
+    // public_root (CircuitCompiler only): the root is that public input of each proof, not the constant `root` - one compiled circuit
+    // then serves membership proofs about different trees; the row, and so the proof, is the same (coefficient -1 on the root)
     (void)depth;
     LinearCombination prev_hash(leaf_val.variable);
     std::vector<LinearCombination> statics;
@@ -936,7 +939,8 @@ inline void vanilla_merkle_merkle_tree_4_verif_gadget(ConstraintSystem& cs, size
         }
     }
     cs.constrain(LinearCombination(constraint_leaf_index));
-    constrain_lc_with_scalar(cs, prev_hash, root);
+    if (public_root) cs.constrain(prev_hash - LinearCombination(*public_root));
+    else constrain_lc_with_scalar(cs, prev_hash, root);
 }
 
 // ---- src/gadget_vsmt_2.rs ------------------------------------------------------------------------
@@ -1048,7 +1052,7 @@ public:
 inline void vanilla_merkle_merkle_tree_verif_gadget(ConstraintSystem& cs, size_t depth, const Scalar& root, const AllocatedScalar& leaf_val,
                                                     const std::vector<AllocatedScalar>& leaf_index_bits, const std::vector<AllocatedScalar>& proof_nodes,
                                                     const std::vector<AllocatedScalar>& statics_, const PoseidonParams& poseidon_params,
-                                                    SboxType sbox_type = SboxType::Inverse) {
+                                                    SboxType sbox_type = SboxType::Inverse, const Variable* public_root = nullptr) {
     LinearCombination prev_hash;
     std::vector<LinearCombination> statics;
     for (auto& s : statics_) statics.push_back(LinearCombination(s.variable));
@@ -1063,7 +1067,8 @@ inline void vanilla_merkle_merkle_tree_verif_gadget(ConstraintSystem& cs, size_t
         LinearCombination right = right_1 + right_2;
         prev_hash = Poseidon_hash_2_constraints(cs, left, right, statics, poseidon_params, sbox_type);
     }
-    constrain_lc_with_scalar(cs, prev_hash, root);
+    if (public_root) cs.constrain(prev_hash - LinearCombination(*public_root));   // (as in the arity-4 gadget above)
+    else constrain_lc_with_scalar(cs, prev_hash, root);
 }
 
 }  // namespace bpr1cs

@@ -93,7 +93,9 @@ struct Scalar {
 
 using CompressedRistretto = std::array<uint8_t, 32>;
 
-enum class VarKind : uint32_t { Committed = 0, MultiplierLeft = 1, MultiplierRight = 2, MultiplierOutput = 3, One = 4 };
+// Public: public input `index` of the proof at hand (BPR1CS_VAR_PUBLIC, include/bpr1cs.h) - understood by CircuitCompiler only, whose
+// circuit serves many proofs; Prover and Verifier build one circuit per proof and keep such constants baked, as the reference does
+enum class VarKind : uint32_t { Committed = 0, MultiplierLeft = 1, MultiplierRight = 2, MultiplierOutput = 3, One = 4, Public = 5 };
 
 struct LinearCombination;
 struct Variable {
@@ -104,6 +106,7 @@ struct Variable {
     static Variable MultiplierRight(uint32_t i) { return {VarKind::MultiplierRight, i}; }
     static Variable MultiplierOutput(uint32_t i) { return {VarKind::MultiplierOutput, i}; }
     static Variable One() { return {VarKind::One, 0}; }
+    static Variable Public(uint32_t k) { return {VarKind::Public, k}; }
     uint32_t encode() const { return ((uint32_t)kind << 28) | index; }
     bool operator==(const Variable& o) const { return kind == o.kind && index == o.index; }
 };
@@ -510,8 +513,10 @@ public:
     void constrain(LinearCombination lc) override { constraints.push_back(std::move(lc)); }
     size_t num_constraints() const override { return constraints.size(); }
     size_t num_multipliers() const override { return num_vars; }
-    // flattened CSR of the constraint list (One terms kept; the device prover drops them)
-    void export_csr(std::vector<uint32_t>& row_off, std::vector<uint32_t>& tvar, std::vector<uint8_t>& tcoeff) const {
+    // flattened CSR of the constraint list (One terms kept; the device prover drops them).  allow_public: CircuitCompiler only - a
+    // Prover's or Verifier's circuit serves ONE proof and its prove / verify call hands over no public block: a Public term there
+    // would make the library read a tail block that is not behind `values` / `commitments`
+    void export_csr(std::vector<uint32_t>& row_off, std::vector<uint32_t>& tvar, std::vector<uint8_t>& tcoeff, bool allow_public = false) const {
         size_t nnz = 0;
         for (auto& lc : constraints) nnz += lc.terms.size();
         row_off.assign(1, 0);
@@ -521,12 +526,17 @@ public:
         size_t k = 0;
         for (auto& lc : constraints) {
             for (auto& t : lc.terms) {
+                if (t.first.kind == VarKind::Public && !allow_public)
+                    throw R1CSError::GadgetError("Variable::Public in a Prover / Verifier: only CircuitCompiler understands public inputs");
+                if (t.first.kind == VarKind::Public && t.second.is_zero()) continue;   // (bpr1cs_circuit_create refuses a public term that says nothing)
                 tvar[k] = t.first.encode();
                 t.second.write_bytes(&tcoeff[32 * k]);
                 k++;
             }
             row_off.push_back((uint32_t)k);
         }
+        tvar.resize(k);
+        tcoeff.resize(32 * k);
     }
 };
 
@@ -599,7 +609,8 @@ public:
                 case VarKind::MultiplierLeft: val = a_L[t.first.index]; break;
                 case VarKind::MultiplierRight: val = a_R[t.first.index]; break;
                 case VarKind::MultiplierOutput: val = a_O[t.first.index]; break;
-                default: val = Scalar::one();
+                case VarKind::One: val = Scalar::one(); break;
+                default: throw R1CSError::GadgetError("Variable::Public in a Prover: only CircuitCompiler understands public inputs");
             }
             acc += t.second * val;
         }

@@ -82,6 +82,27 @@ typedef struct bpr1cs_circuit bpr1cs_circuit; /* the constraint system a Prover 
 #define BPR1CS_VAR_MUL_RIGHT 2u /* Variable::MultiplierRight(i)  */
 #define BPR1CS_VAR_MUL_OUT 3u   /* Variable::MultiplierOutput(i) */
 #define BPR1CS_VAR_ONE 4u       /* Variable::One()               */
+#define BPR1CS_VAR_PUBLIC 5u    /* public input k of THIS proof: a scalar the verifier knows (see "Public inputs" below) */
+
+/* Public inputs.  A constant of the statement that differs from proof to proof - the root of the reference's tree gadgets
+ * (`constrain(prev_hash - root)`, src/gadget_vsmt_4.rs, src/gadget_vsmt_2.rs), a bound - need not be baked into the coefficient of
+ * Variable::One(): a term (BPR1CS_VAR_PUBLIC << 28 | k, coeff) in `term_var` or `lc_var` stands for coeff x p_k, p_k the k-th public
+ * input of the proof at hand.  bpr1cs_circuit_create derives p = 1 + the highest index used (p <= 2^20; p = 0 when the kind does not
+ * occur, and then every call is exactly what it was).  Only a term that uses its input may set p: a public term whose coefficient is
+ * 0 (mod l) is BPR1CS_ERR_INVALID_ARGUMENT (leave the term out).  No entry point reports p: a caller derives it from its own
+ * description by the same rule, and the library - which cannot see how long the caller's arrays are - reads exactly batch x p x 32
+ * bytes behind the committed values / points.  A public input enters LINEARLY with a constant coefficient, like One;
+ * BPR1CS_W_BIT / BPR1CS_W_NOTBIT of one are BPR1CS_ERR_INVALID_ARGUMENT.  A public COEFFICIENT of a wire (the set_i x bit_i of
+ * gadget_set_membership.rs) is a different feature and is not provided.
+ * The values ride in arrays the calls already take, as a tail block:
+ *   prove calls   `values`      = batch x m x 32 committed values, then batch x p x 32 public inputs, proof-major
+ *                 (v_blindings, commitments_out, transcripts: over the m committed values only, as before)
+ *   verify calls  `commitments` = batch x m x 32 points, then batch x p x 32 canonical scalars, proof-major; non-NULL when p > 0
+ * A non-canonical public input: BPR1CS_ERR_INVALID_ARGUMENT for the prover (like every scalar input); for the verifiers that proof
+ * is malformed (verdict 0 / wellformed_out = 0) and the others are judged as always.  Public inputs are NOT appended to the proof's
+ * Merlin transcript - upstream absorbs no constants either -, so a proof is byte for byte the proof of the circuit that has
+ * coeff x p_k folded into its One coefficients, and a verifier running that baked circuit accepts it.  The cross-proof weights DO
+ * bind them (bpr1cs_verify_batch_combined). */
 
 /* Witness-program operand kinds (device-side constraint synthesis). */
 #define BPR1CS_W_LC 0u       /* value of linear combination #arg (cs.multiply / evaluate_lc)   */
@@ -256,7 +277,7 @@ int bpr1cs_gens_table_info(const bpr1cs_gens* g, uint32_t* window_bits, uint32_t
                                          accepts, and no signal.  1 (any other value means 1): every prove job checks its assignment on
                                          the device before its first commitment sum reads the wires - a_L[i] a_R[i] = a_O[i] for every
                                          multiplier i, and sum coeff x value = 0 for every constraint j (row j of the description's CSR;
-                                         value(One) = 1, committed values and wires taken as they were handed in or synthesised) - in
+                                         value(One) = 1, public inputs, committed values and wires taken as they were handed in or synthesised) - in
                                          bpr1cs_prove_batch, _transcripts, _draws and _begin / _end, for host wires and for the device
                                          witness program, on default and BPR1CS_OPT_SECRET_INDEPENDENT handles alike.  A proof whose
                                          assignment fails is REFUSED: its slot of `proofs_out` holds a refusal record instead of a
@@ -298,7 +319,7 @@ size_t bpr1cs_proof_len(const bpr1cs_circuit* c);
 /* Batched Prover::commit x m  +  gadget synthesis  +  Prover::prove
  * (reference src/gadget_vsmt_4.rs:390-434), one independent transcript per proof.
  *   label              Transcript::new(label)
- *   values             batch * m * 32   committed values, proof-major
+ *   values             batch * m * 32   committed values, proof-major (+ batch * p * 32 public inputs behind them, see "Public inputs")
  *   v_blindings        batch * m * 32
  *   rng_seeds          batch * 32       the 32 bytes upstream draws from thread_rng()
  *                                       in TranscriptRng::finalize (made explicit)
@@ -359,7 +380,7 @@ int bpr1cs_prove_batch_end(bpr1cs_job* job, uint8_t* proofs_out, uint8_t* commit
  * commitments and the proof, flatten the constraints and evaluate the single mega-check multiscalar
  * multiplication; ok_out[i] = 1 iff proof i is accepted (R1CSError::VerificationError / FormatError -> 0).
  *   proofs               batch * bpr1cs_proof_len(c)
- *   commitments          batch * m * 32   the V's the verifier `commit`s, in gadget order
+ *   commitments          batch * m * 32   the V's the verifier `commit`s, in gadget order (+ batch * p * 32 public inputs behind them)
  *   verifier_rng_seeds   batch * 32 or NULL (zeros): the 32 bytes upstream draws from thread_rng() for `r`
  * On a handle with BPR1CS_OPT_VERIFY_GROUP = G >= 2 a batch of 2 or more proofs is checked group by group - one combined identity
  * test per G consecutive proofs, the per-proof check only inside a group that fails: per-proof verdicts at close to the cost of
@@ -375,7 +396,11 @@ int bpr1cs_verify_batch(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uin
  *   bind_j  = the proof's own verifier transcript after its last inner-product challenge, cloned,
  *             <- ("ipp_a", a) <- ("ipp_b", b); challenge_bytes("bpr1cs-bind", 32)   (every byte of proof and commitments)
  *   leaf_g  = Transcript("bpr1cs batch leaf") <- u64("leaf", g) <- ("proof", bind_j) for the 32 proofs j = 32g .. 32g+31
- *             (the last leaf may be short); challenge_bytes("leaf", 32)
+ *             (the last leaf may be short); challenge_bytes("leaf", 32).  A circuit with p > 0 public inputs: after each
+ *             proof's ("proof", bind_j) the leaf absorbs ("public", p_j,0 || ... || p_j,p-1) (p x 32 bytes) - the proof's own
+ *             transcript does not hold them, and the B scalar is linear in them: with unbound public inputs and a constant
+ *             batch seed, whoever picks them after seeing the weights could cancel two invalid proofs against each other.
+ *             p = 0: no such message, the derivation is what it was
  *   D       = Transcript("bpr1cs batch verify") <- ("seed", batch_seed) <- u64("base", index_base) <- u64("count", batch)
  *             <- ("leaf", leaf_g) for every leaf in order; challenge_bytes("digest", 32)
  *   rho_j   = Transcript("bpr1cs batch weight") <- ("digest", D) <- u64("j", index_base + j); challenge_scalar("rho")
