@@ -19,6 +19,7 @@ POSEIDON_PARAMS_PATH = os.path.join(_HERE, "data", "poseidon_params_ristretto.bi
 VAR_COMMITTED, VAR_MUL_LEFT, VAR_MUL_RIGHT, VAR_MUL_OUT, VAR_ONE = 0, 1, 2, 3, 4
 VAR_PUBLIC = 5   # public input k of the proof at hand (include/bpr1cs.h "Public inputs"): its value rides in the calls' `publics`
 W_LC, W_INV_LEFT, W_BIT, W_NOTBIT = 0, 1, 2, 3
+W_LCBIT, W_LCNOTBIT = 4, 5    # bit (arg & 0xff) of the canonical value of linear combination #(arg >> 8); 1 - that bit
 
 ERRORS = {0: "OK", -1: "InvalidGeneratorsLength", -2: "FormatError", -3: "VerificationError",
           -4: "MissingAssignment", -5: "GadgetError", -16: "NoDevice", -17: "InvalidArgument", -18: "DeviceError", -19: "OutOfMemory"}
@@ -224,7 +225,7 @@ class Circuit:
     """Flattened constraint system (+ optional device witness program).
 
     constraints: list of rows, each a list of ((kind, index), coeff_int_or_bytes); kind VAR_PUBLIC = public input `index`
-    wops: optional list of (lkind, larg, rkind, rarg); lcs: list of term lists for W_LC operands.
+    wops: optional list of (lkind, larg, rkind, rarg); lcs: list of term lists for W_LC / W_LCBIT / W_LCNOTBIT operands.
     .p: public inputs per proof (1 + the highest index used, as the library derives it; raw=: scanned from the variable list).
     """
 
@@ -665,7 +666,8 @@ def _sc(x):
 class CompiledGadget:
     """A reference gadget compiled (shape only) into a device circuit + witness program.
     The tree gadgets ("vsmt_4", "vsmt_2") compiled WITHOUT sparams take the root as public input 0 of every proof (.p == 1): one
-    circuit then proves and verifies memberships in different trees, `publics` = the roots."""
+    circuit then proves and verifies memberships in different trees, `publics` = the roots.  "bound_check_1" (iparams = [bits], ONE
+    committed value) compiled without sparams takes its bounds as public inputs 0 and 1 (.p == 2), `publics` = (min, max) per proof."""
 
     def __init__(self, name, iparams=(), sparams=(), lib=None, glib=None):
         self.lib = lib or load_library()
@@ -678,7 +680,8 @@ class CompiledGadget:
                                              ctypes.byref(h), ctypes.byref(n), ctypes.byref(q), ctypes.byref(m), ctypes.byref(hw)))
         self.h, self.n, self.q, self.m, self.has_witness_program = h, n.value, q.value, m.value, bool(hw.value)
         self.proof_len = self.lib.bpr1cs_proof_len(h)
-        self.p = 1 if name in ("vsmt_4", "vsmt_2") and len(sparams) == 0 else 0   # (host/frontend.cpp run_gadget: the root as Variable::Public(0))
+        # (host/frontend.cpp run_gadget: the root as Variable::Public(0); the bounds of bound_check_1 as Public(0), Public(1))
+        self.p = {"vsmt_4": 1, "vsmt_2": 1, "bound_check_1": 2}.get(name, 0) if len(sparams) == 0 else 0
 
     def close(self):
         if self.h:

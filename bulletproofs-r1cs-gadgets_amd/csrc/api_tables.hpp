@@ -214,7 +214,10 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
         // a multiplier's operands may only read committed values, the constant, and wires of EARLIER multipliers
         // (the sequential program of K_witness / k_witness_team writes multiplier i after evaluating both operands)
         auto operand_ok = [&](uint32_t kind, uint32_t arg, uint32_t i, bool right) {
-            if (kind == WK_LC) {
+            // (kinds as the caller numbers them: BPR1CS_W_LCBIT / BPR1CS_W_LCNOTBIT carry the combination in arg >> 8 and read what a
+            // BPR1CS_W_LC operand of this multiplier may read)
+            if (kind == WK_LC || kind == BPR1CS_W_LCBIT || kind == BPR1CS_W_LCNOTBIT) {
+                if (kind != WK_LC) arg >>= 8;
                 if (arg >= d->n_lc) return false;
                 for (uint32_t t = d->lc_off[arg]; t < d->lc_off[arg + 1]; t++)
                     if (!var_ok(d->lc_var[t], i)) return false;
@@ -327,7 +330,9 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
     if (d->wops) {
         c->has_program = true;
         std::vector<WOp> ops(d->n);
-        for (uint32_t i = 0; i < d->n; i++) ops[i] = WOp{d->wops[i].lkind, d->wops[i].larg, d->wops[i].rkind, d->wops[i].rarg};
+        // (the caller's kinds 4 and 5 are WK_VAR and WK_ZERO in here: the bit-of-a-combination kinds get internal numbers of their own)
+        auto internal_kind = [](uint32_t kind) { return kind == BPR1CS_W_LCBIT ? WK_LCBIT : kind == BPR1CS_W_LCNOTBIT ? WK_LCNOTBIT : kind; };
+        for (uint32_t i = 0; i < d->n; i++) ops[i] = WOp{internal_kind(d->wops[i].lkind), d->wops[i].larg, internal_kind(d->wops[i].rkind), d->wops[i].rarg};
         uint32_t nt = d->n_lc ? d->lc_off[d->n_lc] : 0;
         std::vector<uint32_t> lo(d->lc_off, d->lc_off + d->n_lc + 1), lv(d->lc_var, d->lc_var + nt);
         // a public input is a read of value row m + k: the prove job lays the public block behind the committed values (v_m), and

@@ -70,6 +70,8 @@ HD inline int tab_digit(const sc& s, uint32_t k, int& carry, const TabCfg& tc) {
 #define WK_ZERO 5u      // empty linear combination
 #define WK_PX 6u        // x of S-box #arg of the Poseidon permutation evaluated last (poseidon_team)
 #define WK_PXINV 7u     // 1/x of that S-box
+#define WK_LCBIT 8u     // BPR1CS_W_LCBIT: bit (arg & 0xff) of the canonical value of linear combination #(arg >> 8)
+#define WK_LCNOTBIT 9u  // BPR1CS_W_LCNOTBIT: 1 - that bit
 
 // ------------------------------------------------------------ fixed-base core
 // acc += s * Base, s canonical (< l).  Signed W-bit digits.  `acc` in the ordinary or the table class (ge_madd_t);
@@ -662,7 +664,14 @@ struct K_witness {  // thread per proof (sequential program)
         if (kind == VK_ONE) return sc_one_mont();
         return W[((size_t)(kind - 1) * n + idx) * B + b];
     }
-    HD sc operand(uint32_t kind, uint32_t arg, uint32_t b) const {
+    // the canonical value of the combination a WK_LCBIT / WK_LCNOTBIT operand named last: a k-bit decomposition names one combination
+    // 2k times in a row.  Valid for the rest of the proof: wires are written once, and bpr1cs_circuit_create lets a combination read
+    // only wires of multipliers before its FIRST use
+    struct LcBits {
+        uint32_t idx = 0xffffffffu;
+        sc x;
+    };
+    HD sc operand(uint32_t kind, uint32_t arg, uint32_t b, LcBits& lcb) const {
         if (kind == WK_VAR) return value(arg, b);
         if (kind == WK_ZERO) return sc_zero();
         if (kind == WK_PX) return scratch(b).at(PX_A, arg);
@@ -672,27 +681,37 @@ struct K_witness {  // thread per proof (sequential program)
             for (uint32_t t = lc_off[arg]; t < lc_off[arg + 1]; t++) acc = sc_add(acc, sc_mul(lc_coeff[t], value(lc_var[t], b)));
             return acc;
         }
+        const uint32_t k = arg & 0xffu;
+        if (kind == WK_LCBIT || kind == WK_LCNOTBIT) {
+            if (lcb.idx != (arg >> 8)) {
+                lcb.x = sc_from_mont(operand(WK_LC, arg >> 8, b, lcb));   // 0 <= x < l < 2^253: bits 253..255 read 0
+                lcb.idx = arg >> 8;
+            }
+            uint32_t bit = (lcb.x.v[k >> 5] >> (k & 31)) & 1u;
+            if (kind == WK_LCNOTBIT) bit ^= 1u;
+            return bit ? sc_one_mont() : sc_zero();
+        }
         sc raw = v_raw[(size_t)(arg >> 8) * B + b];
-        uint32_t k = arg & 0xffu;
         uint32_t bit = (raw.v[k >> 5] >> (k & 31)) & 1u;
         if (kind == WK_NOTBIT) bit ^= 1u;
         return bit ? sc_one_mont() : sc_zero();
     }
     HD void operator()(uint32_t b) const {
         uint32_t pi = 0;
+        LcBits lcb;
         for (uint32_t i = 0; i < n; i++) {
             if (pi < n_perms && perms[pi].first_mul == i) {
                 const PoseidonPerm& pm = perms[pi++];
                 const PoseidonTab& t = ptab[pm.table];
                 sc sh[PS_SIZE];
-                for (uint32_t k = 0; k < t.width; k++) sh[PS_N + k] = operand(WK_LC, pm.in_lc[k], b);
+                for (uint32_t k = 0; k < t.width; k++) sh[PS_N + k] = operand(WK_LC, pm.in_lc[k], b, lcb);
                 poseidon_team(t, pconst, scratch(b), sh, 8, 0, pm.first_mul, pm.covers);
                 if (pm.covers) { i += pm.covers - 1; continue; }
             }
             WOp op = ops[i];
-            sc l = operand(op.lkind, op.larg, b);
+            sc l = operand(op.lkind, op.larg, b, lcb);
             W[((size_t)0 * n + i) * B + b] = l;
-            sc r = (op.rkind == WK_INV_LEFT) ? sc_invert(l) : operand(op.rkind, op.rarg, b);
+            sc r = (op.rkind == WK_INV_LEFT) ? sc_invert(l) : operand(op.rkind, op.rarg, b, lcb);
             W[((size_t)1 * n + i) * B + b] = r;
             W[((size_t)2 * n + i) * B + b] = sc_mul(l, r);
         }

@@ -43,8 +43,26 @@ struct WireCache {
     uint32_t idx[2];
     sc l[2], r[2], o[2];
 };
+// the team's value of linear combination #j: the terms spread over the lanes, every lane ends with the sum
 template <int T>
-__device__ inline sc team_operand(const K_witness& p, uint32_t kind, uint32_t arg, uint32_t b, uint32_t lane, const WireCache& wc, bool& fenced) {
+__device__ inline sc team_lc(const K_witness& p, uint32_t j, uint32_t b, uint32_t lane, bool& fenced) {
+    if (!fenced) { __threadfence_block(); fenced = true; }  // earlier wires are read back from memory
+    sc acc = sc_zero();
+    uint32_t t1 = p.lc_off[j + 1];
+    for (uint32_t t = p.lc_off[j] + lane; t < t1; t += T) acc = sc_add(acc, sc_mul(p.lc_coeff[t], p.value(p.lc_var[t], b)));
+    return team_sum<T>(acc);
+}
+// WK_LCBIT / WK_LCNOTBIT: the canonical value of the combination named last stays in LDS, in the team's own slot behind its Poseidon
+// area (`slot` = team_sh[team] + PS_SIZE).  Every lane of the team holds the same sum and stores it there - the same bytes to the same
+// address - and reads back only after its own store, so no barrier is needed.  Between operands the cache costs k_witness_team no
+// vector register: the slot hangs off the `sh` pointer the kernel holds anyway, `idx` is wave-uniform (the program is the same for
+// every proof), and taking a bit is one LDS read.
+template <int T>
+__device__ inline void team_lcbits_fill(const K_witness& p, uint32_t j, uint32_t b, uint32_t lane, bool& fenced, sc* slot) {
+    *slot = sc_from_mont(team_lc<T>(p, j, b, lane, fenced));   // 0 <= x < l < 2^253: bits 253..255 read 0
+}
+template <int T>
+__device__ inline sc team_operand(const K_witness& p, uint32_t kind, uint32_t arg, uint32_t b, uint32_t lane, const WireCache& wc, bool& fenced, uint32_t& lcb_idx, sc* lcb) {
     if (kind == WK_ZERO) return sc_zero();
     if (kind == WK_PX) return p.scratch(b).at(PX_A, arg);      // written (and fenced) by poseidon_team
     if (kind == WK_PXINV) return p.scratch(b).at(PX_INVA, arg);
@@ -58,12 +76,16 @@ __device__ inline sc team_operand(const K_witness& p, uint32_t kind, uint32_t ar
         }
         return p.value(arg, b);
     }
-    if (kind == WK_LC) {
-        if (!fenced) { __threadfence_block(); fenced = true; }  // earlier wires are read back from memory
-        sc acc = sc_zero();
-        uint32_t t1 = p.lc_off[arg + 1];
-        for (uint32_t t = p.lc_off[arg] + lane; t < t1; t += T) acc = sc_add(acc, sc_mul(p.lc_coeff[t], p.value(p.lc_var[t], b)));
-        return team_sum<T>(acc);
+    if (kind == WK_LC) return team_lc<T>(p, arg, b, lane, fenced);
+    if (kind == WK_LCBIT || kind == WK_LCNOTBIT) {
+        const uint32_t j = arg >> 8, k = arg & 0xffu;
+        if (lcb_idx != j) {
+            team_lcbits_fill<T>(p, j, b, lane, fenced, lcb);
+            lcb_idx = j;
+        }
+        uint32_t bit = (lcb->v[k >> 5] >> (k & 31u)) & 1u;
+        if (kind == WK_LCNOTBIT) bit ^= 1u;
+        return bit ? sc_one_mont() : sc_zero();
     }
     sc raw = p.v_raw[(size_t)(arg >> 8) * p.B + b];
     uint32_t k = arg & 0xffu;
@@ -81,15 +103,17 @@ __global__ void __launch_bounds__(64) k_witness_team(K_witness p) {
     WireCache wc;
     wc.idx[0] = wc.idx[1] = 0xffffffffu;
     bool fenced = true;
-    __shared__ sc team_sh[64 / T][PS_SIZE];
+    __shared__ sc team_sh[64 / T][PS_SIZE + 1];   // (+ 1: the team's WK_LCBIT value, team_lcbits_fill)
     sc* sh = team_sh[(threadIdx.x & 63u) / T];
+    sc* const lcb = sh + PS_SIZE;
+    uint32_t lcb_idx = 0xffffffffu;
     uint32_t pi = 0;
     for (uint32_t i = 0; i < p.n; i++) {
         if (pi < p.n_perms && p.perms[pi].first_mul == i) {  // an annotated Poseidon permutation starts here
             const PoseidonPerm pm = p.perms[pi++];
             const PoseidonTab t = p.ptab[pm.table];
             for (uint32_t k = 0; k < t.width; k++) {
-                sc v = team_operand<T>(p, WK_LC, pm.in_lc[k], b, lane, wc, fenced);
+                sc v = team_operand<T>(p, WK_LC, pm.in_lc[k], b, lane, wc, fenced, lcb_idx, lcb);
                 if (lane == 0) sh[PS_N + k] = v;
             }
             __syncthreads();
@@ -101,8 +125,8 @@ __global__ void __launch_bounds__(64) k_witness_team(K_witness p) {
             }
         }
         WOp op = p.ops[i];
-        sc l = team_operand<T>(p, op.lkind, op.larg, b, lane, wc, fenced);
-        sc r = (op.rkind == WK_INV_LEFT) ? sc_invert(l) : team_operand<T>(p, op.rkind, op.rarg, b, lane, wc, fenced);
+        sc l = team_operand<T>(p, op.lkind, op.larg, b, lane, wc, fenced, lcb_idx, lcb);
+        sc r = (op.rkind == WK_INV_LEFT) ? sc_invert(l) : team_operand<T>(p, op.rkind, op.rarg, b, lane, wc, fenced, lcb_idx, lcb);
         sc o = sc_mul(l, r);
         if (lane == 0 && active) {
             p.W[((size_t)0 * p.n + i) * p.B + b] = l;

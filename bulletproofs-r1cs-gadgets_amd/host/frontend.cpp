@@ -176,8 +176,29 @@ bpr1cs_circuit* CircuitCompiler::finish(uint32_t* n_out, uint32_t* q_out, uint32
             lc_off.push_back((uint32_t)lc_var.size());
             return (uint32_t)(lc_off.size() - 2);
         };
+        // bits of a combination: one entry per combination OBJECT handed to WitnessHint::bit_of_lc (a k-bit decomposition hands the same
+        // one in 2k times in a row; the terms are compared as well, so an address that a later object reuses starts a new entry)
+        const void* bits_object = nullptr;
+        const LinearCombination* bits_lc = nullptr;
+        uint32_t bits_index = 0;
+        auto same_terms = [](const LinearCombination& a, const LinearCombination& b) {
+            if (a.terms.size() != b.terms.size()) return false;
+            for (size_t i = 0; i < a.terms.size(); i++)
+                if (a.terms[i].first.encode() != b.terms[i].first.encode() || !(a.terms[i].second == b.terms[i].second)) return false;
+            return true;
+        };
+        auto add_bits_lc = [&](const WitnessHint& h) {
+            if (!(bits_lc && h.lc_object == bits_object && same_terms(h.lc, *bits_lc))) {
+                bits_index = add_lc(h.lc);
+                bits_object = h.lc_object;
+                bits_lc = &h.lc;     // (a hint of `ops`, which outlives this loop)
+            }
+            return (bits_index << 8) | h.bit;
+        };
         auto enc = [&](const WitnessHint& h, uint32_t& kind, uint32_t& arg) {
             switch (h.kind) {
+                case WitnessHint::LcBit: kind = BPR1CS_W_LCBIT; arg = add_bits_lc(h); break;
+                case WitnessHint::LcNotBit: kind = BPR1CS_W_LCNOTBIT; arg = add_bits_lc(h); break;
                 case WitnessHint::LC: kind = BPR1CS_W_LC; arg = add_lc(h.lc); break;
                 case WitnessHint::InverseOfLeft: kind = BPR1CS_W_INV_LEFT; arg = 0; break;
                 case WitnessHint::Bit: kind = BPR1CS_W_BIT; arg = (h.committed << 8) | h.bit; break;
@@ -261,6 +282,22 @@ static size_t run_gadget(const GadgetSpec& g, Harness& h) {
         auto v = AQ(0), a = AQ(1), b = AQ(2);
         bound_check_gadget(h.cs, v, a, b, u64_of(g.ip, 3), u64_of(g.ip, 1), g.ip.at(0));
         return 3;
+    }
+    if (g.name == "bound_check_1") {  // min <= v <= max with ONE commitment: the bits of v - min and of max - v are bits of linear
+        // combinations (BPR1CS_W_LCBIT), not of committed values.  ip = [bits]; sp = [min, max] bakes the bounds (the only form Prover
+        // and Verifier support); COMPILED without sp the bounds are public inputs 0 and 1 of every proof
+        const size_t bits = g.ip.at(0);
+        if (bits > 252) throw R1CSError::GadgetError("bound_check_1: at most 252 bits");
+        const bool bounds_public = g.sp.empty() && dynamic_cast<CircuitCompiler*>(&h.cs) != nullptr;
+        const Variable v = h.commit(0);
+        const LinearCombination mn = bounds_public ? LinearCombination(Variable::Public(0)) : LinearCombination(g.sp.at(0));
+        const LinearCombination mx = bounds_public ? LinearCombination(Variable::Public(1)) : LinearCombination(g.sp.at(1));
+        const LinearCombination a = LinearCombination(v) - mn, b = mx - LinearCombination(v);
+        std::optional<Scalar> va, vb;
+        if (auto val = h.value(0)) { va = *val - g.sp.at(0); vb = g.sp.at(1) - *val; }
+        positive_no_gadget_lc(h.cs, a, va, bits);
+        positive_no_gadget_lc(h.cs, b, vb, bits);
+        return 1;
     }
     if (g.name == "set_membership") {  // src/gadget_set_membership.rs:93-134 ; ip = [k, items(lo,hi)...]
         size_t k = g.ip.at(0);

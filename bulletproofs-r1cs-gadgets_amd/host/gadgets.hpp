@@ -52,6 +52,31 @@ inline void positive_no_gadget(ConstraintSystem& cs, const AllocatedQuantity& v,
     cs.constrain(LinearCombination(constraint_v));
 }
 
+// positive_no_gadget for a DERIVED value: the shape of r1cs_utils.rs:20-48 with the value given by a linear combination - v - min, a
+// product wire, a hash output, v - Public(0) - so that a range check needs no commitment beside the value it is about.  `value`: the
+// combination's value (provers), its bits are those of its canonical representative 0 <= x < l.  Sound for bit_size <= 252 (2^252 < l).
+inline void positive_no_gadget_lc(ConstraintSystem& cs, const LinearCombination& lc, const std::optional<Scalar>& value, size_t bit_size) {
+    LinearCombination sum = -lc;
+    Scalar exp_2 = Scalar::one();
+    std::array<uint8_t, 32> bytes{};
+    if (value) bytes = value->to_bytes();
+    const bool hints = cs.uses_witness_hints();
+    for (size_t i = 0; i < bit_size; i++) {
+        std::optional<std::pair<Scalar, Scalar>> asg;
+        if (value) {
+            uint64_t bit = i < 256 ? (bytes[i >> 3] >> (i & 7)) & 1u : 0u;
+            asg = std::make_pair(Scalar(1 - bit), Scalar(bit));
+        }
+        MulVars mv = cs.allocate_multiplier(asg, hints ? WitnessHint::bit_of_lc(lc, (uint32_t)i, true) : WitnessHint(),
+                                            hints ? WitnessHint::bit_of_lc(lc, (uint32_t)i, false) : WitnessHint());
+        cs.constrain(LinearCombination(mv.out));
+        cs.constrain(mv.left + (mv.right - 1u));
+        sum.terms.push_back({mv.right, exp_2});
+        exp_2 = exp_2 + exp_2;
+    }
+    cs.constrain(sum);
+}
+
 // ---- src/factors.rs:12-21 -----------------------------------------------------
 inline void factors(ConstraintSystem& cs, const AllocatedScalar& p, const AllocatedScalar& q, const Scalar& r) {
     MulVars mv = cs.multiply(LinearCombination(p.variable), LinearCombination(q.variable));

@@ -267,10 +267,11 @@ struct AllocatedScalar {
 // Extension over the reference API (default = none): gadgets that pass hints can be
 // compiled into a device witness program; without hints the Prover path still works.
 struct WitnessHint {
-    enum Kind { None, LC, InverseOfLeft, Bit, NotBit } kind = None;
-    LinearCombination lc;       // LC
+    enum Kind { None, LC, InverseOfLeft, Bit, NotBit, LcBit, LcNotBit } kind = None;
+    LinearCombination lc;       // LC, LcBit / LcNotBit
     uint32_t committed = 0;     // Bit / NotBit: index of the committed value
     uint32_t bit = 0;
+    const void* lc_object = nullptr;   // LcBit / LcNotBit: the combination object handed in (CircuitCompiler: one `lc` entry per object)
     static WitnessHint of_lc(const LinearCombination& l) { WitnessHint h; h.kind = LC; h.lc = l; return h; }
     static WitnessHint inverse_of_left() { WitnessHint h; h.kind = InverseOfLeft; return h; }
     static WitnessHint bit_of(const Variable& v, uint32_t k, bool negate) {
@@ -279,6 +280,17 @@ struct WitnessHint {
         h.committed = v.index;
         h.bit = k;
         if (v.kind != VarKind::Committed) h.kind = None;
+        return h;
+    }
+    // bit k of the canonical value (0 <= x < l) of a DERIVED value: BPR1CS_W_LCBIT / BPR1CS_W_LCNOTBIT.  Hand in the same object for every
+    // bit of one decomposition; the combination may read committed values, One, public inputs and wires of earlier multipliers
+    static WitnessHint bit_of_lc(const LinearCombination& l, uint32_t k, bool negate) {
+        WitnessHint h;
+        h.kind = negate ? LcNotBit : LcBit;
+        h.lc = l;
+        h.lc_object = &l;
+        h.bit = k;
+        if (k > 255) h.kind = None;
         return h;
     }
 };

@@ -109,6 +109,18 @@ typedef struct bpr1cs_circuit bpr1cs_circuit; /* the constraint system a Prover 
 #define BPR1CS_W_INV_LEFT 1u /* right wire = inverse of this multiplier's left wire (Inverse S-box, gadget_poseidon.rs:160-166) */
 #define BPR1CS_W_BIT 2u      /* bit (arg & 0xff) of committed value (arg >> 8)  (gadget_vsmt_4.rs:226-238, r1cs_utils.rs:28-31) */
 #define BPR1CS_W_NOTBIT 3u   /* 1 - that bit */
+#define BPR1CS_W_LCBIT 4u    /* bit (arg & 0xff) of the canonical value x, 0 <= x < l, of linear combination #(arg >> 8) */
+#define BPR1CS_W_LCNOTBIT 5u /* 1 - that bit */
+/* BPR1CS_W_LCBIT / BPR1CS_W_LCNOTBIT give the bits of a DERIVED value - v - min, a product wire, a hash output, v - Public(0) - so that
+ * a range check needs no commitment beside v.  Either may be a left or a right operand.  The combination index is < n_lc (and < 2^24:
+ * it shares `arg` with the bit index); the combination may read what a BPR1CS_W_LC operand of the same multiplier may read - committed
+ * values, One, public inputs, wires of EARLIER multipliers - and BPR1CS_ERR_INVALID_ARGUMENT is returned for an index >= n_lc and for a
+ * combination that reads the multiplier's own or a later wire, as for BPR1CS_W_LC.  l < 2^253: bits 253..255 are always 0 (NOTBIT: 1).
+ * A combination only these kinds refer to counts towards p like any other.  The value is evaluated once per run of operands that
+ * name the same combination (a k-bit decomposition names it 2k times in a row), so list the bits of one value together.  A
+ * description that uses neither kind is byte for byte what it was.
+ * BPR1CS_W_INV_LEFT of a left wire of 0 yields 0 (Scalar::invert's ladder does the same; safegcd: 0 -> 0), so the multiplier's
+ * output is 0 where the left wire is 0 and 1 elsewhere: the witness of an "is zero" test on a derived value. */
 
 typedef struct {
     uint32_t lkind, larg, rkind, rarg;
