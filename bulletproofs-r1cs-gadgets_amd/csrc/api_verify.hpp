@@ -76,16 +76,8 @@ static void verify_front(VerifyCtx& v, const bpr1cs_gens* g, const bpr1cs_circui
         launch_sum_partials(B, K_sum_partials{v.dpart.p, v.delta.p, B, N}, st);
     }
     sc* wc = v.wvec.p + (size_t)(3 * n + m + p) * B;
-    if (p) {   // w_c += sum_k (column of public input k) x p_k; a non-canonical public input makes its proof malformed
-        K_verify_public kpub{v.wvec.p + (size_t)(3 * n + m) * B, v.d_pub, wc, v.fail.p, B, p};
-#if !defined(BPR1CS_HOSTSIM)
-        if (B <= FINISH_WAVE_MAX_PROOFS) {
-            hipLaunchKernelGGL(k_verify_public_wave, dim3(B), dim3(64), 0, st, kpub);
-            HIPCHK(hipGetLastError());
-        } else
-#endif
-        launch(B, kpub, st);
-    }
+    // w_c += sum_k (column of public input k) x p_k; a non-canonical public input makes its proof malformed
+    if (p) launch_verify_public(K_verify_public{v.wvec.p + (size_t)(3 * n + m) * B, v.d_pub, wc, v.fail.p, B, p}, st);
     launch(B, K_verify_bscalars{v.chal.p, wc, v.delta.p, v.bsc.p, B}, st);
     v.P = 8 + m + 2 * lgN;
 }
@@ -134,16 +126,7 @@ static int verify_batch_once(const bpr1cs_gens* g, const bpr1cs_circuit* c, cons
         kp.out = pts.p;
         launch((uint64_t)v.P * B, kp, st);
     }
-    {
-        K_verify_finish kf{g->tab.p, g->tc, partial.p, pts.p, v.bsc.p, v.fail.p, ok.p, B, plan.nchunks, n_pts};
-#if !defined(BPR1CS_HOSTSIM)
-        if (B <= FINISH_WAVE_MAX_PROOFS) {
-            hipLaunchKernelGGL(k_verify_finish_wave, dim3(B), dim3(64), 0, st, kf);
-            HIPCHK(hipGetLastError());
-        } else
-#endif
-        launch(B, kf, st);
-    }
+    launch_verify_finish(K_verify_finish{g->tab.p, g->tc, partial.p, pts.p, v.bsc.p, v.fail.p, ok.p, B, plan.nchunks, n_pts}, st);
     dev_d2h(ok_out, ok.p, sizeof(int) * B, st);
     stats.collect();
     return BPR1CS_OK;
@@ -170,29 +153,34 @@ static void verify_weights(CombinedCtx& k, VerifyCtx& v, const uint8_t* batch_se
     launch(1, K_batch_digest{k.d_bseed.p, leaf.p, k.digest.p, index_base, B}, st);
     launch(B, K_batch_weights{k.digest.p, k.rho.p, index_base}, st);
 }
+// every proof's own points times its weight: k.pts[P][B]; a point that does not decode sets its proof's flag
+static void verify_weighted_points(CombinedCtx& k, VerifyCtx& v, dev_stream_t st) {
+    const uint32_t B = v.B;
+    k.pts.alloc((size_t)v.P * B);
+    K_verify_points kp{v.d_pf.p, v.d_vc.p, v.chal.p, v.uk.p, v.wvec.p + (size_t)3 * v.n * B, k.pts.p, v.fail.p, B, v.m, v.lgN, (uint32_t)v.plen};
+    kp.rho = k.rho.p;
+    launch((uint64_t)v.P * B, kp, st);
+}
+// sums of 64 points, level after level, until at most 64 points are left: -> where they sit (cur itself or one of red[]), cnt updated
+static const ge* reduce_to_64_points(const ge* cur, uint32_t& cnt, DevBuf<ge> red[2], dev_stream_t st) {
+    for (int flip = 0; cnt > 64; flip ^= 1) {
+        const uint32_t outc = (cnt + 63) / 64;
+        red[flip].alloc(outc);
+        launch(outc, K_ge_reduce{cur, red[flip].p, 1, cnt, 64}, st);
+        cur = red[flip].p;
+        cnt = outc;
+    }
+    return cur;
+}
 static void verify_combine(CombinedCtx& k, VerifyCtx& v, const uint8_t* batch_seed, uint64_t index_base, dev_stream_t st) {
     const uint32_t B = v.B, N = v.N;
     verify_weights(k, v, batch_seed, index_base, st);
     k.cgh.alloc((size_t)2 * N); k.cb.alloc(2);
     launch((uint64_t)2 * N, K_combine_scalars{v.gh.p, k.rho.p, k.cgh.p, B}, st);
     launch(2, K_combine_scalars{v.bsc.p, k.rho.p, k.cb.p, B}, st);
-    k.pts.alloc((size_t)v.P * B);
-    K_verify_points kp{v.d_pf.p, v.d_vc.p, v.chal.p, v.uk.p, v.wvec.p + (size_t)3 * v.n * B, k.pts.p, v.fail.p, B, v.m, v.lgN, (uint32_t)v.plen};
-    kp.rho = k.rho.p;
-    launch((uint64_t)v.P * B, kp, st);
-    const ge* cur = k.pts.p;
-    uint32_t cnt = v.P * B;
-    int flip = 0;
-    while (cnt > 64) {
-        uint32_t outc = (cnt + 63) / 64;
-        k.red[flip].alloc(outc);
-        launch(outc, K_ge_reduce{cur, k.red[flip].p, 1, cnt, 64}, st);
-        cur = k.red[flip].p;
-        cnt = outc;
-        flip ^= 1;
-    }
-    k.own = cur;
-    k.own_cnt = cnt;
+    verify_weighted_points(k, v, st);
+    k.own_cnt = v.P * B;
+    k.own = reduce_to_64_points(k.pts.p, k.own_cnt, k.red, st);
 }
 
 // Cross-proof batched verification: one identity test for the whole batch (and, summed over ranks, for the whole job).
@@ -218,16 +206,9 @@ static int verify_batch_combined_once(const bpr1cs_gens* g, const bpr1cs_circuit
     MsmPlan plan;
     MsmSeg sg{k.cgh.p, N, N, N, 0, baseG, 0}, sh{k.cgh.p + N, N, N, N, 0, baseH, 0};
     run_msm(g, sg, sh, 1, partial, plan, st, &stats);
-    const ge* mcur = partial.p;
     uint32_t mcnt = plan.nchunks;
     DevBuf<ge> mred[2];
-    for (int f = 0; mcnt > 64; f ^= 1) {
-        uint32_t outc = (mcnt + 63) / 64;
-        mred[f].alloc(outc);
-        launch(outc, K_ge_reduce{mcur, mred[f].p, 1, mcnt, 64}, st);
-        mcur = mred[f].p;
-        mcnt = outc;
-    }
+    const ge* mcur = reduce_to_64_points(partial.p, mcnt, mred, st);
     DevBuf<uint8_t> d_out(32);
     DevBuf<int> d_wf(1);
     launch(1, K_batch_finish{g->tab.p, g->tc, mcur, k.own, k.cb.p, v.fail.p, d_out.p, d_wf.p, mcnt, k.own_cnt, v.B}, st);
@@ -240,25 +221,27 @@ static int verify_batch_combined_once(const bpr1cs_gens* g, const bpr1cs_circuit
 
 // Grouped verification (BPR1CS_OPT_VERIFY_GROUP): the batch in NG = ceil(B / G) groups of G consecutive proofs, one combined
 // identity test per group - the shared-base sum is one fixed-base MSM of batch NG over the segmented combination cgh[2N][NG] of the
-// proofs' scalar vectors - and the per-proof path only for the proofs of a group that fails (verify_batch_grouped_once).
-// Workgroups (one wavefront each) of k_combine_scalars_group_wave for rows x NG outputs.  A launch must stay below 2^32 threads in
-// all, and the depth-32 circuit (2N = 65536 rows) passes 2^26 outputs at NG = 1024 - 4096 proofs in groups of 4: the grid is capped and
+// proofs' scalar vectors.  What happens to a group that fails is BPR1CS_OPT_VERIFY_GROUP_FALLBACK: nothing more (0: its proofs are rejected),
+// the per-proof path for its well-formed proofs (1, verify_batch_grouped_once) or bisection on the device (2).  One routine,
+// verify_batch_bisect_once, serves all three: the groups are the ranges of its depth 0, and modes 0 and 1 stop there.
+// Workgroups (one wavefront each) of k_combine_scalars_range_wave for rows x R outputs.  A launch must stay below 2^32 threads in
+// all, and the depth-32 circuit (2N = 65536 rows) passes 2^26 outputs at R = 1024 - 4096 proofs in groups of 4: the grid is capped and
 // a wavefront walks outputs a grid apart (2^20 wavefronts are 128 times what the chip holds at once; a 4096-proof job with G = 64 is
-// four outputs per wavefront).  The output index itself must fit 32 bits (verify_args_ok bounds 4N x batch, and NG <= (batch + 1) / 2).
+// four outputs per wavefront).  The output index itself must fit 32 bits (verify_args_ok bounds 4N x batch, and R <= (batch + 1) / 2).
 static const uint32_t GROUP_COMBINE_MAX_WGS = 1u << 20;
 static uint32_t combine_grouped_wgs(uint64_t rows, uint64_t NG) {
     const uint64_t outputs = rows * NG;
     if (rows > 0xffffffffull || NG > 0xffffffffull || outputs > 0xffffffffull) throw DevError{BPR1CS_ERR_INVALID_ARGUMENT};
     return (uint32_t)std::min<uint64_t>(outputs, GROUP_COMBINE_MAX_WGS);
 }
-static void launch_combine_grouped(uint32_t rows, const K_combine_scalars_grouped& f, dev_stream_t st) {
-    const uint32_t wgs = combine_grouped_wgs(rows, f.NG);
+static void launch_combine_ranges(uint32_t rows, const K_combine_scalars_ranges& f, dev_stream_t st) {
+    const uint32_t wgs = combine_grouped_wgs(rows, f.R);
     if (!wgs) return;
 #if !defined(BPR1CS_HOSTSIM)
-    hipLaunchKernelGGL(k_combine_scalars_group_wave, dim3(wgs), dim3(64), 0, st, f, rows * f.NG);
+    hipLaunchKernelGGL(k_combine_scalars_range_wave, dim3(wgs), dim3(64), 0, st, f, rows * f.R);
     HIPCHK(hipGetLastError());
 #else
-    launch((uint64_t)rows * f.NG, f, st);
+    launch((uint64_t)rows * f.R, f, st);
 #endif
 }
 #if defined(BPR1CS_HOSTSIM)
@@ -272,10 +255,19 @@ extern "C" int bpr1cs_sim_group_combine_grid(uint64_t rows, uint64_t NG, uint32_
     API_CATCH
 }
 #endif
-// the device part: -> gok[NG] (the group's identity test held and none of its proofs is malformed), pfail[B] (proof is malformed)
-static int verify_groups_device(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len, const uint8_t* proofs,
-                                const uint8_t* commitments, const uint8_t* verifier_rng_seeds, size_t batch, uint32_t G,
-                                std::vector<int>& gok, std::vector<int>& pfail) {
+// The device part of all three modes.  S(R) = sum_{b in R, fail[b] = 0} rho_b E_b is additive over the proofs of a range R, and
+// everything it is made of - gh, bsc, the weights, the weighted own points - stays on the device.  Depth 0 tests the groups: one
+// range combination, one run_msm of batch NG and one range finish.  `descend` = false (modes 0 and 1) ends there with group
+// verdicts: a group holds iff its S is the identity and none of its proofs is malformed.  `descend` = true (mode 2) is
+// level-synchronous bisection: every later depth takes the failing ranges of more than one proof of ALL groups, computes S of their
+// left halves (ceil(s / 2) proofs) with one range combination, one run_msm whose batch is the number of ranges and one range finish -
+// which also forms S(right) = S(parent) - S(left) - and reads the identity flags back.  A passing range accepts its well-formed
+// proofs, a failing range of one proof rejects it.  Nothing is uploaded again and the per-proof path is not taken.
+// -> ok_out[B], pfail[B] (proof is malformed)
+struct BisectRange { uint32_t lo, hi, pt; };   // a failing range of more than one proof; pt: where its S sits among the depth's points
+static int verify_batch_bisect_once(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,
+                                    const uint8_t* proofs, const uint8_t* commitments, const uint8_t* verifier_rng_seeds, size_t batch,
+                                    uint32_t G, bool descend, int* ok_out, std::vector<int>& pfail) {
     API_TRY
     dev_stream_t st = g->stream;
     CallScope scope(st);
@@ -288,126 +280,16 @@ static int verify_groups_device(const bpr1cs_gens* g, const bpr1cs_circuit* c, c
     if (verifier_rng_seeds) memcpy(bseed, verifier_rng_seeds, 32);
     CombinedCtx k;
     verify_weights(k, v, bseed, 0, st);
-    k.cgh.alloc((size_t)2 * N * NG); k.cb.alloc((size_t)2 * NG);
-    launch_combine_grouped(2 * N, K_combine_scalars_grouped{v.gh.p, k.rho.p, k.cgh.p, B, G, NG}, st);
-    launch_combine_grouped(2, K_combine_scalars_grouped{v.bsc.p, k.rho.p, k.cb.p, B, G, NG}, st);
-    k.pts.alloc((size_t)v.P * B);
-    K_verify_points kp{v.d_pf.p, v.d_vc.p, v.chal.p, v.uk.p, v.wvec.p + (size_t)3 * v.n * B, k.pts.p, v.fail.p, B, v.m, v.lgN, (uint32_t)v.plen};
-    kp.rho = k.rho.p;
-    launch((uint64_t)v.P * B, kp, st);
-    DevBuf<ge> gpts(NG);
-    DevBuf<int> gfail(NG), ok(NG);
-    {
-        K_group_points kg{k.pts.p, v.fail.p, gpts.p, gfail.p, B, v.P, G};
-#if !defined(BPR1CS_HOSTSIM)
-        hipLaunchKernelGGL(k_group_points_wave, dim3(NG), dim3(64), 0, st, kg);
-        HIPCHK(hipGetLastError());
-#else
-        launch(NG, kg, st);
-#endif
-    }
-    DevBuf<ge> partial;
-    MsmPlan plan;
-    MsmSeg sg{k.cgh.p, N, N, N, 0, baseG, 0}, sh{k.cgh.p + (size_t)N * NG, N, N, N, 0, baseH, 0};
-    run_msm(g, sg, sh, NG, partial, plan, st, &stats);
-    {
-        K_verify_finish kf{g->tab.p, g->tc, partial.p, gpts.p, k.cb.p, gfail.p, ok.p, NG, plan.nchunks, 1};
-#if !defined(BPR1CS_HOSTSIM)
-        if (NG <= FINISH_WAVE_MAX_PROOFS) {
-            hipLaunchKernelGGL(k_verify_finish_wave, dim3(NG), dim3(64), 0, st, kf);
-            HIPCHK(hipGetLastError());
-        } else
-#endif
-        launch(NG, kf, st);
-    }
-    gok.resize(NG); pfail.resize(B);
-    dev_d2h(gok.data(), ok.p, sizeof(int) * NG, st);
-    dev_d2h(pfail.data(), v.fail.p, sizeof(int) * B, st);
-    stats.collect();
-    return BPR1CS_OK;
-    API_CATCH
-}
-static int verify_batch_grouped_once(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,
-                                     const uint8_t* proofs, const uint8_t* commitments, const uint8_t* verifier_rng_seeds, size_t batch,
-                                     uint32_t G, bool fallback, int* ok_out) {
-    if (!ok_out) return BPR1CS_ERR_INVALID_ARGUMENT;
-    int rc = verify_args_ok(g, c, label, proofs, commitments, batch);
-    if (rc) return rc;
-    std::vector<int> gok, pfail;
-    rc = verify_groups_device(g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, G, gok, pfail);
-    if (rc) return rc;
-    API_TRY
-    std::vector<size_t> redo;   // well-formed proofs of the groups that failed
-    for (size_t b = 0; b < batch; b++) {
-        ok_out[b] = gok[b / G];
-        if (!gok[b / G] && !pfail[b] && fallback) redo.push_back(b);
-    }
-    if (redo.empty()) return BPR1CS_OK;
-    // the inputs are host memory: the sub-batch is gathered here and takes the per-proof path as a batch of its own
-    const size_t plen = bpr1cs_proof_len(c), clen = (size_t)c->m * 32, ulen = (size_t)c->p * 32;   // (public inputs: the tail block of both arrays)
-    const uint8_t* pub = commitments ? commitments + batch * clen : nullptr;
-    std::vector<uint8_t> sp(redo.size() * plen), sc_(redo.size() * (clen + ulen) + 1), ss(verifier_rng_seeds ? redo.size() * 32 : 0);
-    std::vector<int> sok(redo.size(), 0);
-    for (size_t i = 0; i < redo.size(); i++) {
-        memcpy(sp.data() + i * plen, proofs + redo[i] * plen, plen);
-        if (clen) memcpy(sc_.data() + i * clen, commitments + redo[i] * clen, clen);
-        if (ulen) memcpy(sc_.data() + redo.size() * clen + i * ulen, pub + redo[i] * ulen, ulen);
-        if (verifier_rng_seeds) memcpy(ss.data() + i * 32, verifier_rng_seeds + redo[i] * 32, 32);
-    }
-    rc = verify_batch_once(g, c, label, label_len, sp.data(), sc_.data(), verifier_rng_seeds ? ss.data() : nullptr, redo.size(), sok.data());
-    if (rc) return rc;
-    for (size_t i = 0; i < redo.size(); i++) ok_out[redo[i]] = sok[i];
-    return BPR1CS_OK;
-    API_CATCH
-}
-
-// Bisection inside a failing group (BPR1CS_OPT_VERIFY_GROUP_FALLBACK = 2).  S(R) = sum_{b in R, fail[b] = 0} rho_b E_b is
-// additive over the proofs of a range R, and everything it is made of - gh, bsc, the weights, the weighted own points - is still on the
-// device when a group fails.  Level-synchronous: depth 0 tests the groups; every later depth takes the failing ranges of more than one
-// proof of ALL groups, computes S of their left halves (ceil(s / 2) proofs) with one range combination, one run_msm whose batch is the
-// number of ranges and one range finish - which also forms S(right) = S(parent) - S(left) - and reads the identity flags back.  A
-// passing range accepts its well-formed proofs, a failing range of one proof rejects it.  Nothing is uploaded again and the per-proof
-// path is not taken.
-struct BisectRange { uint32_t lo, hi, pt; };   // a failing range of more than one proof; pt: where its S sits among the depth's points
-static void launch_combine_ranges(uint32_t rows, const K_combine_scalars_ranges& f, dev_stream_t st) {
-    const uint32_t wgs = combine_grouped_wgs(rows, f.R);   // (the grid cap and the 32-bit output index of the grouped combination)
-    if (!wgs) return;
-#if !defined(BPR1CS_HOSTSIM)
-    hipLaunchKernelGGL(k_combine_scalars_range_wave, dim3(wgs), dim3(64), 0, st, f, rows * f.R);
-    HIPCHK(hipGetLastError());
-#else
-    launch((uint64_t)rows * f.R, f, st);
-#endif
-}
-static int verify_batch_bisect_once(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,
-                                    const uint8_t* proofs, const uint8_t* commitments, const uint8_t* verifier_rng_seeds, size_t batch,
-                                    uint32_t G, int* ok_out) {
-    if (!ok_out) return BPR1CS_ERR_INVALID_ARGUMENT;
-    int rc = verify_args_ok(g, c, label, proofs, commitments, batch);
-    if (rc) return rc;
-    API_TRY
-    dev_stream_t st = g->stream;
-    CallScope scope(st);
-    MsmStats stats;
-    VerifyCtx v;
-    verify_front(v, g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, true, st);
-    const uint32_t B = v.B, N = v.N, NG = (B + G - 1) / G, baseG = 2, baseH = 2 + g->cap;
-    uint8_t bseed[32] = {0};   // as verify_groups_device: the first proof's verifier seed
-    if (verifier_rng_seeds) memcpy(bseed, verifier_rng_seeds, 32);
-    CombinedCtx k;
-    verify_weights(k, v, bseed, 0, st);
     // the own points first: a point that does not decode sets its proof's flag, and the sums below leave such a proof out
-    k.pts.alloc((size_t)v.P * B);
-    K_verify_points kp{v.d_pf.p, v.d_vc.p, v.chal.p, v.uk.p, v.wvec.p + (size_t)3 * v.n * B, k.pts.p, v.fail.p, B, v.m, v.lgN, (uint32_t)v.plen};
-    kp.rho = k.rho.p;
-    launch((uint64_t)v.P * B, kp, st);
+    verify_weighted_points(k, v, st);
     // scratch of a slice of at most NG ranges - what depth 0 needs - shared by all depths
     k.cgh.alloc((size_t)2 * N * NG); k.cb.alloc((size_t)2 * NG);
     DevBuf<ge> rpts(NG), partial, spts[2];   // spts: S of the ranges of this depth and of the one before (the parents)
     std::vector<BisectRange> cur(NG), next;
     for (uint32_t grp = 0; grp < NG; grp++) cur[grp] = BisectRange{grp * G, std::min(B, (grp + 1) * G), 0};
-    std::vector<int> pfail(B), zero;
+    std::vector<int> zero;
     std::vector<uint32_t> h_rng;
+    pfail.resize(B);
     for (uint32_t depth = 0; !cur.empty(); depth++) {
         const uint32_t R = (uint32_t)cur.size();
         h_rng.resize((size_t)3 * R);   // lo | hi | parent of the tested ranges: the groups at depth 0, the left halves below
@@ -428,33 +310,26 @@ static int verify_batch_bisect_once(const bpr1cs_gens* g, const bpr1cs_circuit* 
             const uint32_t *lo = d_rng.p + off, *hi = d_rng.p + R + off, *par = d_rng.p + 2 * (size_t)R + off;
             launch_combine_ranges(2 * N, K_combine_scalars_ranges{v.gh.p, k.rho.p, v.fail.p, lo, hi, k.cgh.p, B, cnt}, st);
             launch_combine_ranges(2, K_combine_scalars_ranges{v.bsc.p, k.rho.p, v.fail.p, lo, hi, k.cb.p, B, cnt}, st);
-            {
-                K_range_points kr{k.pts.p, v.fail.p, lo, hi, rpts.p, B, v.P};
-#if !defined(BPR1CS_HOSTSIM)
-                hipLaunchKernelGGL(k_range_points_wave, dim3(cnt), dim3(64), 0, st, kr);
-                HIPCHK(hipGetLastError());
-#else
-                launch(cnt, kr, st);
-#endif
-            }
+            launch_range_points(K_range_points{k.pts.p, v.fail.p, lo, hi, rpts.p, B, v.P}, cnt, st);
             MsmPlan plan;
             MsmSeg sg{k.cgh.p, N, N, N, 0, baseG, 0}, sh{k.cgh.p + (size_t)N * cnt, N, N, N, 0, baseH, 0};
             run_msm(g, sg, sh, cnt, partial, plan, st, &stats);
-            K_range_finish kf{g->tab.p, g->tc, partial.p, rpts.p, k.cb.p, parent, par, out.p + off, out.p + R + off,
-                              d_zero.p + off, d_zero.p + R + off, cnt, plan.nchunks};
-#if !defined(BPR1CS_HOSTSIM)
-            if (cnt <= FINISH_WAVE_MAX_PROOFS) {
-                hipLaunchKernelGGL(k_range_finish_wave, dim3(cnt), dim3(64), 0, st, kf);
-                HIPCHK(hipGetLastError());
-            } else
-#endif
-            launch(cnt, kf, st);
+            launch_range_finish(K_range_finish{g->tab.p, g->tc, partial.p, rpts.p, k.cb.p, parent, par, out.p + off, out.p + R + off,
+                                               d_zero.p + off, d_zero.p + R + off, cnt, plan.nchunks}, st);
         }
         zero.resize((size_t)2 * R);
         dev_d2h(zero.data(), d_zero.p, sizeof(int) * (depth ? 2 * (size_t)R : R), st);
         if (depth == 0) {
             dev_d2h(pfail.data(), v.fail.p, sizeof(int) * B, st);
             for (uint32_t b = 0; b < B; b++) ok_out[b] = !pfail[b];   // a malformed proof is rejected and is part of no sum
+            if (!descend) {   // group verdicts (a group's S leaves its malformed proofs out: their flags fail the group here)
+                for (uint32_t i = 0; i < R; i++) {
+                    int good = zero[i];
+                    for (uint32_t b = cur[i].lo; b < cur[i].hi; b++) good &= !pfail[b];
+                    for (uint32_t b = cur[i].lo; b < cur[i].hi; b++) ok_out[b] = good;
+                }
+                break;
+            }
         }
         next.clear();
         auto classify = [&](uint32_t lo, uint32_t hi, uint32_t pt, int is_zero) {
@@ -471,6 +346,38 @@ static int verify_batch_bisect_once(const bpr1cs_gens* g, const bpr1cs_circuit* 
         cur.swap(next);
     }
     stats.collect();
+    return BPR1CS_OK;
+    API_CATCH
+}
+static int verify_batch_grouped_once(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,
+                                     const uint8_t* proofs, const uint8_t* commitments, const uint8_t* verifier_rng_seeds, size_t batch,
+                                     uint32_t G, int mode, int* ok_out) {
+    if (!ok_out) return BPR1CS_ERR_INVALID_ARGUMENT;
+    int rc = verify_args_ok(g, c, label, proofs, commitments, batch);
+    if (rc) return rc;
+    std::vector<int> pfail;
+    rc = verify_batch_bisect_once(g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, G,
+                                  mode == BPR1CS_VERIFY_GROUP_FALLBACK_BISECT, ok_out, pfail);
+    if (rc || mode != BPR1CS_VERIFY_GROUP_FALLBACK_RECHECK) return rc;
+    API_TRY
+    std::vector<size_t> redo;   // well-formed proofs of the groups that failed
+    for (size_t b = 0; b < batch; b++)
+        if (!ok_out[b] && !pfail[b]) redo.push_back(b);
+    if (redo.empty()) return BPR1CS_OK;
+    // the inputs are host memory: the sub-batch is gathered here and takes the per-proof path as a batch of its own
+    const size_t plen = bpr1cs_proof_len(c), clen = (size_t)c->m * 32, ulen = (size_t)c->p * 32;   // (public inputs: the tail block of both arrays)
+    const uint8_t* pub = commitments ? commitments + batch * clen : nullptr;
+    std::vector<uint8_t> sp(redo.size() * plen), sc_(redo.size() * (clen + ulen) + 1), ss(verifier_rng_seeds ? redo.size() * 32 : 0);
+    std::vector<int> sok(redo.size(), 0);
+    for (size_t i = 0; i < redo.size(); i++) {
+        memcpy(sp.data() + i * plen, proofs + redo[i] * plen, plen);
+        if (clen) memcpy(sc_.data() + i * clen, commitments + redo[i] * clen, clen);
+        if (ulen) memcpy(sc_.data() + redo.size() * clen + i * ulen, pub + redo[i] * ulen, ulen);
+        if (verifier_rng_seeds) memcpy(ss.data() + i * 32, verifier_rng_seeds + redo[i] * 32, 32);
+    }
+    rc = verify_batch_once(g, c, label, label_len, sp.data(), sc_.data(), verifier_rng_seeds ? ss.data() : nullptr, redo.size(), sok.data());
+    if (rc) return rc;
+    for (size_t i = 0; i < redo.size(); i++) ok_out[redo[i]] = sok[i];
     return BPR1CS_OK;
     API_CATCH
 }
@@ -544,10 +451,7 @@ extern "C" int bpr1cs_verify_batch(const bpr1cs_gens* g, const bpr1cs_circuit* c
     const int G = g ? g->opts.verify_group.load() : 0;
     if (G >= 2 && batch >= 2) {
         const int mode = g->opts.verify_group_fallback.load();
-        if (mode == BPR1CS_VERIFY_GROUP_FALLBACK_BISECT)
-            return with_scratch_retry(g, [&] { return verify_batch_bisect_once(g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, (uint32_t)G, ok_out); });
-        const bool fallback = mode != BPR1CS_VERIFY_GROUP_FALLBACK_NONE;
-        return with_scratch_retry(g, [&] { return verify_batch_grouped_once(g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, (uint32_t)G, fallback, ok_out); });
+        return with_scratch_retry(g, [&] { return verify_batch_grouped_once(g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, (uint32_t)G, mode, ok_out); });
     }
     return with_scratch_retry(g, [&] { return verify_batch_once(g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, ok_out); });
 }

@@ -2023,46 +2023,13 @@ struct K_combine_scalars {  // gid = row : out[row] = sum_b in[row*B + b] * rho[
         out[row] = acc;
     }
 };
-// Grouped verification (BPR1CS_OPT_VERIFY_GROUP): the batch in groups of G consecutive proofs (the last may be short), one combined check per
-// group.  These functors are the definition of the two segmented sums; on the device a wavefront computes each output
-// (kernels_hip.hpp k_combine_scalars_group_wave, k_group_points_wave) - sums mod l and sums of points do not depend on the order.
-struct K_combine_scalars_grouped {  // gid = row*NG + grp : out[gid] = sum_{b in group grp} in[row*B + b] * rho[b]   (forms as K_combine_scalars)
-    const sc* in;
-    const sc* rho;  // Montgomery
-    sc* out;        // [rows][NG]
-    uint32_t B, G, NG;
-    HD void operator()(uint32_t g) const {
-        const uint32_t row = g / NG, grp = g % NG;
-        const uint32_t lo = grp * G, hi = lo + G < B ? lo + G : B;
-        sc acc = sc_zero();
-        const sc* r = in + (size_t)row * B;
-        for (uint32_t b = lo; b < hi; b++) acc = sc_add(acc, sc_mul(r[b], rho[b]));
-        out[g] = acc;
-    }
-};
-struct K_group_points {  // gid = grp : out[grp] = sum of the P weighted points of every proof of the group, gfail[grp] = OR of its proofs' flags
-    const ge* pts;    // [P][B]
-    const int* fail;  // [B]
-    ge* out;          // [NG]
-    int* gfail;       // [NG]
-    uint32_t B, P, G;
-    HD void operator()(uint32_t grp) const {
-        const uint32_t lo = grp * G, hi = lo + G < B ? lo + G : B;
-        ge acc = ge_identity();
-        int bad = 0;
-        for (uint32_t b = lo; b < hi; b++) {
-            for (uint32_t p = 0; p < P; p++) acc = ge_add_ge(acc, pts[(size_t)p * B + b]);
-            bad |= fail[b] != 0;
-        }
-        out[grp] = acc;
-        gfail[grp] = bad;
-    }
-};
-// Bisection inside a failing group (BPR1CS_OPT_VERIFY_GROUP_FALLBACK = 2): the same two segmented sums over arbitrary ranges
-// [lo[r], hi[r]) of proofs - the groups themselves at level 0, the left halves of the failing ranges below - from which the malformed
-// proofs (fail[b] != 0) are left out: S(R) = sum_{b in R, fail[b] = 0} rho_b E_b is additive over proofs, so one MSM column per split
-// and a point subtraction give both children.  Wavefront forms: kernels_hip.hpp k_combine_scalars_range_wave, k_range_points_wave,
-// k_range_finish_wave.
+// Grouped verification (BPR1CS_OPT_VERIFY_GROUP): the batch in groups of G consecutive proofs (the last may be short), one
+// combined check per group, and with BPR1CS_OPT_VERIFY_GROUP_FALLBACK = 2 bisection inside a group that fails.  The two segmented sums
+// run over arbitrary ranges [lo[r], hi[r]) of proofs - the groups themselves at depth 0, the left halves of the failing ranges below -
+// from which the malformed proofs (fail[b] != 0) are left out: S(R) = sum_{b in R, fail[b] = 0} rho_b E_b is additive over proofs,
+// so one MSM column per split and a point subtraction give both children.  These functors are the definition of the sums; on the
+// device a wavefront computes each output (kernels_hip.hpp k_combine_scalars_range_wave, k_range_points_wave, k_range_finish_wave) -
+// sums mod l and sums of points do not depend on the order.
 struct K_combine_scalars_ranges {  // gid = row*R + r : out[gid] = sum_{b in [lo[r], hi[r]), fail[b] = 0} in[row*B + b] * rho[b]   (forms as K_combine_scalars)
     const sc* in;
     const sc* rho;       // Montgomery

@@ -412,57 +412,15 @@ __global__ void __launch_bounds__(64) k_verify_finish_wave(K_verify_finish f) {
     if (lane == 0) f.ok[b] = (!f.fail[b]) && bytes_are_zero32(enc);
 }
 
-// Grouped verification (BPR1CS_OPT_VERIFY_GROUP): K_combine_scalars_grouped with a wavefront per (row, group).  The proofs of a group are
-// consecutive b of one row, so lane l takes proofs lo + l, lo + l + 64 ... - a wavefront's loads of a row and of the weights are
-// contiguous (K_combine_scalars walks its row with one thread: 4096 dependent products per output at the benchmarked batch) - and the
-// butterfly adds the 64 partial sums (mod l: the order does not matter).  Output g = row*NG + grp; the grid is capped
-// (combine_grouped_wgs in api_verify.hpp: a launch may not have 2^32 threads or more), a wavefront takes outputs blockIdx.x,
-// blockIdx.x + gridDim.x ... - g is the same for all its lanes, so they stay together through the shuffles.
-__global__ void __launch_bounds__(64) k_combine_scalars_group_wave(K_combine_scalars_grouped f, uint32_t outputs) {
-    const uint32_t lane = threadIdx.x;
-    for (uint64_t g = blockIdx.x; g < outputs; g += gridDim.x) {
-        const uint32_t row = (uint32_t)g / f.NG, grp = (uint32_t)g % f.NG;
-        const uint32_t lo = grp * f.G, hi = lo + f.G < f.B ? lo + f.G : f.B;
-        const sc* r = f.in + (size_t)row * f.B;
-        sc acc = sc_zero();
-        for (uint32_t b = lo + lane; b < hi; b += 64u) acc = sc_add(acc, sc_mul(r[b], f.rho[b]));
-#pragma unroll 1
-        for (int sft = 32; sft > 0; sft >>= 1) {
-            sc o;
-#pragma unroll
-            for (int i = 0; i < 8; i++) o.v[i] = (uint32_t)__shfl_xor((int)acc.v[i], sft, 64);
-            acc = sc_add(acc, o);
-        }
-        if (lane == 0) f.out[g] = acc;
-    }
-}
-// K_group_points with a wavefront per group: the group's cnt x P weighted points are items (p, j) -> pts[p*B + lo + j], consecutive
-// lanes on consecutive proofs of one p; the butterfly adds the lanes' sums, the group's flag is the OR over its proofs' flags.
-__global__ void __launch_bounds__(64) k_group_points_wave(K_group_points f) {
-    const uint32_t grp = blockIdx.x, lane = threadIdx.x;
-    const uint32_t lo = grp * f.G, hi = lo + f.G < f.B ? lo + f.G : f.B, cnt = hi - lo;
-    ge acc = ge_identity();
-    for (uint32_t idx = lane; idx < cnt * f.P; idx += 64u) {
-        const uint32_t p = idx / cnt, j = idx - p * cnt;
-        acc = ge_add_ge(acc, f.pts[(size_t)p * f.B + lo + j]);
-    }
-    int bad = 0;
-    for (uint32_t b = lo + lane; b < hi; b += 64u) bad |= f.fail[b] != 0;
-#pragma unroll 1
-    for (int sft = 32; sft > 0; sft >>= 1) {
-        acc = ge_add_ge(acc, ge_shfl_xor(acc, sft));
-        bad |= __shfl_xor(bad, sft, 64);
-    }
-    if (lane == 0) {
-        f.out[grp] = acc;
-        f.gfail[grp] = bad;
-    }
-}
-
-// Bisection inside a failing group (BPR1CS_OPT_VERIFY_GROUP_FALLBACK = 2): the three wavefront forms of K_combine_scalars_ranges,
-// K_range_points and K_range_finish.  K_combine_scalars_ranges with a wavefront per (row, range): as k_combine_scalars_group_wave, with
-// the range's bounds read from lo[] / hi[] (the same for all lanes) and a malformed proof's term left out - lanes stay together
-// through the shuffles, a skipped lane adds zero.  Output g = row*R + r; the grid is capped the same way.
+// Grouped verification (BPR1CS_OPT_VERIFY_GROUP, and bisection inside a failing group with BPR1CS_OPT_VERIFY_GROUP_FALLBACK = 2): the three
+// wavefront forms of K_combine_scalars_ranges, K_range_points and K_range_finish.  K_combine_scalars_ranges with a wavefront per
+// (row, range).  The proofs of a range are consecutive b of one row, so lane l takes proofs lo + l, lo + l + 64 ... - a wavefront's
+// loads of a row and of the weights are contiguous (K_combine_scalars walks its row with one thread: 4096 dependent products per
+// output at the benchmarked batch) - and the butterfly adds the 64 partial sums (mod l: the order does not matter).  The range's
+// bounds are read from lo[] / hi[] (the same for all lanes) and a malformed proof's term is left out: a skipped lane adds zero.
+// Output g = row*R + r; the grid is capped (combine_grouped_wgs in api_verify.hpp: a launch may not have 2^32 threads or more), a
+// wavefront takes outputs blockIdx.x, blockIdx.x + gridDim.x ... - g is the same for all its lanes, so they stay together through
+// the shuffles.
 __global__ void __launch_bounds__(64) k_combine_scalars_range_wave(K_combine_scalars_ranges f, uint32_t outputs) {
     const uint32_t lane = threadIdx.x;
     for (uint64_t g = blockIdx.x; g < outputs; g += gridDim.x) {
@@ -482,7 +440,8 @@ __global__ void __launch_bounds__(64) k_combine_scalars_range_wave(K_combine_sca
         if (lane == 0) f.out[g] = acc;
     }
 }
-// K_range_points with a wavefront per range: items (p, j) -> pts[p*B + lo + j] as in k_group_points_wave, those of a malformed proof skipped
+// K_range_points with a wavefront per range: the range's cnt x P weighted points are items (p, j) -> pts[p*B + lo + j], consecutive
+// lanes on consecutive proofs of one p, those of a malformed proof skipped; the butterfly adds the lanes' sums.
 __global__ void __launch_bounds__(64) k_range_points_wave(K_range_points f) {
     const uint32_t r = blockIdx.x, lane = threadIdx.x;
     const uint32_t lo = f.lo[r], hi = f.hi[r], cnt = hi - lo;

@@ -111,6 +111,45 @@ static void launch_pow_tables(const K_pow_tables& f, uint32_t B, dev_stream_t st
 #endif
     launch((uint64_t)3 * B, f, st);
 }
+// the verifier's per-proof and per-range kernels: a wavefront per output for a handful of outputs, a lane per output above
+static void launch_verify_public(const K_verify_public& f, dev_stream_t st) {
+#if !defined(BPR1CS_HOSTSIM)
+    if (f.B <= FINISH_WAVE_MAX_PROOFS) {
+        hipLaunchKernelGGL(k_verify_public_wave, dim3(f.B), dim3(64), 0, st, f);
+        HIPCHK(hipGetLastError());
+        return;
+    }
+#endif
+    launch(f.B, f, st);
+}
+static void launch_verify_finish(const K_verify_finish& f, dev_stream_t st) {
+#if !defined(BPR1CS_HOSTSIM)
+    if (f.B <= FINISH_WAVE_MAX_PROOFS) {
+        hipLaunchKernelGGL(k_verify_finish_wave, dim3(f.B), dim3(64), 0, st, f);
+        HIPCHK(hipGetLastError());
+        return;
+    }
+#endif
+    launch(f.B, f, st);
+}
+static void launch_range_points(const K_range_points& f, uint32_t R, dev_stream_t st) {   // (a wavefront per range whatever R: a range is up to G x P points)
+#if !defined(BPR1CS_HOSTSIM)
+    hipLaunchKernelGGL(k_range_points_wave, dim3(R), dim3(64), 0, st, f);
+    HIPCHK(hipGetLastError());
+#else
+    launch(R, f, st);
+#endif
+}
+static void launch_range_finish(const K_range_finish& f, dev_stream_t st) {
+#if !defined(BPR1CS_HOSTSIM)
+    if (f.R <= FINISH_WAVE_MAX_PROOFS) {
+        hipLaunchKernelGGL(k_range_finish_wave, dim3(f.R), dim3(64), 0, st, f);
+        HIPCHK(hipGetLastError());
+        return;
+    }
+#endif
+    launch(f.R, f, st);
+}
 static void launch_finish(const K_msm_finish& f, uint32_t B, dev_stream_t st) {
 #if !defined(BPR1CS_HOSTSIM)
     if (B <= FINISH_WAVE_MAX_PROOFS && !f.extra_pt) {

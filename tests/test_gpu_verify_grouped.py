@@ -1,5 +1,6 @@
-"""Grouped batch verification (BPR1CS_OPT_VERIFY_GROUP) on the device: the wavefront kernels k_combine_scalars_group_wave and
-k_group_points_wave (csrc/kernels_hip.hpp), the fixed-base MSM with batch = number of groups and the group finish, through the C ABI.
+"""Grouped batch verification (BPR1CS_OPT_VERIFY_GROUP) on the device: the wavefront kernels k_combine_scalars_range_wave,
+k_range_points_wave and k_range_finish_wave (csrc/kernels_hip.hpp) with the groups as ranges and the fixed-base MSM with batch = number of
+groups, through the C ABI.
 Cases and checker: tests/verify_group_cases.py (the reference is the per-proof path on a default handle); the simulator twin is
 tests/test_verify_grouped.py.  The runs with BPR1CS_OPT_VERIFY_GROUP_FALLBACK = 0 are the ones that show what the kernels computed."""
 import pytest
@@ -45,6 +46,16 @@ def test_malformed_proofs_and_swapped_commitment_gpu(e):
     V.check_malformed(e, "b141_g70")
 
 
+def test_malformed_lone_proof_of_the_last_group_gpu(e):
+    """B = 9, G = 4, proof 8 malformed: the last group's sums run over no proof at all - the identity - and the group fails by the flag"""
+    V.check_malformed_at(e, "b9_g4", 8)
+
+
+def test_malformed_proof_in_a_lanes_second_pass_gpu(e):
+    """B = 141, G = 70, proof 65 malformed: lane 1 of the combining wavefront holds proofs 1 and 65, the skipped term is in its second pass"""
+    V.check_malformed_at(e, "b141_g70", 65)
+
+
 def test_null_seeds_gpu(e):
     assert V.verify_null_seeds(e, "b9_g4", 0) == [True] * 9
     assert V.verify_null_seeds(e, "b6_g4", 1) == [True] * 6
@@ -70,7 +81,7 @@ def test_off_switches_gpu(e):
 
 def test_more_outputs_than_the_combining_grid_gpu(e, hip_lib, hip_glib):
     """260 four-level tree proofs (N = 4096: 8192 rows) in groups of 2: 8192 x 130 outputs are more than the 2^20 wavefronts
-    k_combine_scalars_group_wave is launched with at most (csrc/api_verify.hpp GROUP_COMBINE_MAX_WGS; a launch of 2^32 threads is
+    k_combine_scalars_range_wave is launched with at most (csrc/api_verify.hpp GROUP_COMBINE_MAX_WGS; a launch of 2^32 threads is
     refused by the runtime), so wavefronts take a second output a grid apart - and 130 groups are more than the MSM's lane path
     takes.  Proofs made by the library from the benchmark's workload generator (the oracle would need a minute per proof)."""
     import importlib

@@ -1,5 +1,6 @@
 """Grouped batch verification (BPR1CS_OPT_VERIFY_GROUP) on the CPU simulator: the functor forms of the segmented sums
-(csrc/kernels.hpp K_combine_scalars_grouped, K_group_points), the host logic around them, the off switches and the options.
+(csrc/kernels.hpp K_combine_scalars_ranges, K_range_points, K_range_finish with the groups as ranges), the host logic around them, the
+off switches and the options.
 Cases and checker: tests/verify_group_cases.py; the wavefront kernels run in tests/test_gpu_verify_grouped.py.
 
 Left out here: "vsmt_b3_g2" (N = 4096 is minutes on the simulator); "b141_g70" runs valid and with its tampered positions (69, 70,
@@ -52,6 +53,17 @@ def test_malformed_proofs_and_swapped_commitment(e):
     V.check_malformed(e, "b9_g4")
 
 
+def test_malformed_lone_proof_of_the_last_group(e):
+    """B = 9, G = 4, proof 8 malformed: the last group's sums run over no proof at all - the identity - and the group fails by the flag"""
+    V.check_malformed_at(e, "b9_g4", 8)
+
+
+def test_malformed_proof_in_a_lanes_second_pass(e):
+    """B = 141, G = 70, proof 65 malformed (a point that does not decode): lane 1 of the combining wavefront holds proofs 1 and 65.
+    One call per mode, without the reference call (the shape is slow here; the device runs all three forms)"""
+    V.check_malformed_at(e, "b141_g70", 65, forms=(0,), reference=False)
+
+
 def test_null_seeds(e):
     assert V.verify_null_seeds(e, "b9_g4", 0) == [True] * 9
     assert V.verify_null_seeds(e, "b6_g4", 1) == [True] * 6
@@ -97,7 +109,7 @@ def test_off_switches_are_todays_path(e):
 
 
 def test_combining_launch_stays_below_the_thread_limit(sim_lib):
-    """A launch of 2^32 threads or more is refused by the HIP runtime.  k_combine_scalars_group_wave has one 64-lane workgroup per output
+    """A launch of 2^32 threads or more is refused by the HIP runtime.  k_combine_scalars_range_wave has one 64-lane workgroup per output
     up to a cap and walks the rest a grid apart; the host function that sizes it (csrc/api_verify.hpp combine_grouped_wgs, here through
     a simulator-only export) is asked for shapes no test can afford to run: the depth-32 circuit (65536 rows) with 4096 proofs in groups of
     4 - exactly 2^32 threads at a workgroup per output -, of 2, 16384 proofs in groups of 1 .. 16, a depth-253 circuit (524288 rows)"""

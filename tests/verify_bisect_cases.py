@@ -105,10 +105,7 @@ def check_every_single_position(e, name):
         check_tampered(e, name, {pos}, mode1=False)
 
 
-def malformed_forms(p):
-    """the three forms of verify_group_cases.check_malformed: a first point that does not decode (found by K_verify_points, after the
-    transcript stage), a non-canonical t_x and version byte 1 (found by the transcript stage)"""
-    return [p[:1] + b"\xff" * 32 + p[33:], p[:T_X] + b"\xff" * 32 + p[T_X + 32:], b"\x01" + p[1:]]
+malformed_forms = VG.malformed_forms
 
 
 def check_malformed(e, name, pos, also_tampered=()):

@@ -158,14 +158,28 @@ def check_two_tampered(e, name, pairs):
             check(e, name, P, b["C"][:B], {x, y}, seeds=seeds, reference=i == 0)
 
 
+def malformed_forms(p):
+    """proof p with a first point that does not decode (found by K_verify_points, after the transcript stage), with a non-canonical t_x
+    and with version byte 1 (both found by the transcript stage)"""
+    return [p[:1] + b"\xff" * 32 + p[33:], p[:T_X] + b"\xff" * 32 + p[T_X + 32:], b"\x01" + p[1:]]
+
+
+def check_malformed_at(e, name, pos, forms=(0, 1, 2), reference=True):
+    """proof `pos` malformed among good proofs, in the given forms of malformed_forms: the range sums of modes 0 and 1 leave a
+    malformed proof out, so its group must fail by the proof's flag (mode 0 rejects the whole group, mode 1 the proof alone)"""
+    kind, B, G = CASES[name]
+    b = e.batch(kind, B)
+    P = b["P"][:B]
+    for f in forms:
+        check(e, name, P[:pos] + [malformed_forms(P[pos])[f]] + P[pos + 1:], b["C"][:B], {pos}, reference=reference)
+
+
 def check_malformed(e, name):
     """in proof 0: a first point that does not decode, a non-canonical t_x, version byte 1; then a commitment swapped between two
     groups (both fail)"""
     kind, B, G = CASES[name]
     b = e.batch(kind, B)
-    p0 = b["P"][0]
-    for broken in (p0[:1] + b"\xff" * 32 + p0[33:], p0[:T_X] + b"\xff" * 32 + p0[T_X + 32:], b"\x01" + p0[1:]):
-        check(e, name, [broken] + b["P"][1:B], b["C"][:B], {0})
+    check_malformed_at(e, name, 0)
     C = [list(c) for c in b["C"][:B]]
     C[0][0], C[G][0] = C[G][0], C[0][0]
     check(e, name, b["P"][:B], C, {0, G})
