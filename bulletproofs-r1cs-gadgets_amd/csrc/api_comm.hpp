@@ -15,7 +15,7 @@ enum { BP_NCCL_SUCCESS = 0, BP_NCCL_UINT8 = 1 };     // ncclSuccess, ncclUint8
 typedef int (*bp_nccl_get_unique_id_fn)(bp_nccl_unique_id*);
 typedef int (*bp_nccl_comm_init_rank_fn)(bp_nccl_comm*, int, bp_nccl_unique_id, int);
 typedef int (*bp_nccl_comm_destroy_fn)(bp_nccl_comm);
-typedef int (*bp_nccl_all_gather_fn)(const void*, void*, size_t, int, bp_nccl_comm, void* /* hipStream_t */);
+typedef int (*bp_nccl_all_gather_fn)(const void*, void*, size_t, int, bp_nccl_comm, void* /* the runtime's stream handle */);
 struct RcclApi {
     bp_nccl_get_unique_id_fn get_unique_id = nullptr;
     bp_nccl_comm_init_rank_fn comm_init_rank = nullptr;
@@ -45,11 +45,6 @@ static RcclApi& rccl_api() {
     }();
     return api;
 }
-static void comm_release_cached() {
-#if !defined(BPR1CS_HOSTSIM)
-    dev_pool().release_all();
-#endif
-}
 struct bpr1cs_comm {
     int rank = 0, world = 1;
     bool owned = false;
@@ -78,12 +73,12 @@ extern "C" int bpr1cs_comm_create(const uint8_t id[128], int rank, int world, bp
         // RCCL allocates its own device buffers: when this library's allocator cache holds the rest of the device, give it back
         // and try once more (only where no other rank is waiting inside the same collective initialisation)
         if (rccl_api().comm_init_rank(&c->comm, world, uid, rank) != BP_NCCL_SUCCESS) {
-            comm_release_cached();
+            dev_release_cache();
             bp_nccl_unique_id uid2;
             if (rccl_api().get_unique_id(&uid2) != BP_NCCL_SUCCESS || rccl_api().comm_init_rank(&c->comm, 1, uid2, 0) != BP_NCCL_SUCCESS) { delete c; return BPR1CS_ERR_DEVICE; }
         }
     } else {
-        comm_release_cached();   // before the ranks meet: cached blocks are of no use to RCCL
+        dev_release_cache();   // before the ranks meet: cached blocks are of no use to RCCL
         if (rccl_api().comm_init_rank(&c->comm, world, uid, rank) != BP_NCCL_SUCCESS) { delete c; return BPR1CS_ERR_DEVICE; }
     }
     *out = c;

@@ -124,9 +124,7 @@ struct CallScope {
     explicit CallScope(dev_stream_t s) : prev(dev_deferred_frees()), st(s) { dev_deferred_frees() = &frees; }
     ~CallScope() {
         dev_deferred_frees() = prev;
-#if !defined(BPR1CS_HOSTSIM)
-        (void)hipStreamSynchronize(st);
-#endif
+        dev_sync_quiet(st);
         for (void* p : frees) dev_free_now(p);
     }
 };
@@ -290,17 +288,8 @@ static bool circuit_desc_equal(const bpr1cs_circuit* c, const bpr1cs_circuit_des
     return c->k_term_var.size() == nnz && memcmp(c->k_row_off.data(), d->row_off, ((size_t)d->q + 1) * 4) == 0 &&
            memcmp(c->k_term_var.data(), d->term_var, (size_t)nnz * 4) == 0 && memcmp(c->k_term_coeff.data(), d->term_coeff, (size_t)nnz * 32) == 0;
 }
-static int current_device() {
-#if defined(BPR1CS_HOSTSIM)
-    return 0;
-#else
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-    return dev;
-#endif
-}
 static bpr1cs_circuit* circuit_cache_lookup(const bpr1cs_circuit_desc* d, uint64_t key) {
-    const int dev = current_device();
+    const int dev = dev_current();
     CircuitCache& cc = circuit_cache();
     std::lock_guard<std::mutex> lk(cc.mu);
     for (bpr1cs_circuit* c : cc.items)
@@ -332,7 +321,7 @@ static void circuit_cache_insert(bpr1cs_circuit* c, const bpr1cs_circuit_desc* d
     c->k_term_var.assign(d->term_var, d->term_var + nnz);
     c->k_term_coeff.assign(d->term_coeff, d->term_coeff + (size_t)nnz * 32);
     c->cache_key = key;
-    c->cache_device = current_device();
+    c->cache_device = dev_current();
     c->cache_refs = 1;
     std::vector<bpr1cs_circuit*> dead;
     {
@@ -362,15 +351,7 @@ static void circuit_cache_purge() {
     for (auto* x : dead) delete x;
 }
 
-static bool have_device() {
-#if defined(BPR1CS_HOSTSIM)
-    return true;
-#else
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return false;
-    return n > 0;
-#endif
-}
+static bool have_device() { return dev_count() > 0; }
 
 template <class T>
 static void upload(DevBuf<T>& d, const std::vector<T>& h, dev_stream_t s) {

@@ -19,16 +19,7 @@ extern "C" int bpr1cs_poseidon_permutation_batch(const bpr1cs_poseidon_params* p
     upload(d_pc, pc, st);
     upload(d_in, hin, st);
     K_poseidon_batch k{t, d_pc.p, d_in.p, d_out.p, sbox_inverse ? 1u : 0u};
-#if defined(BPR1CS_HOSTSIM)
-    launch(n, k, st);
-#else
-    if (sbox_inverse) {
-        hipLaunchKernelGGL(k_poseidon_team, dim3((n + 7) / 8), dim3(64), 0, st, k, n);
-        HIPCHK(hipGetLastError());
-    } else {
-        launch(n, k, st);
-    }
-#endif
+    if (!LAUNCH_WAVE_FORM(sbox_inverse, (n + 7) / 8, st, k_poseidon_team, k, n)) launch(n, k, st);   // (teams of 8 lanes: 8 permutations per wavefront)
     dev_d2h(hout.data(), d_out.p, hout.size() * sizeof(sc), st);
     for (size_t i = 0; i < hout.size(); i++) sc_mont_tobytes(hout[i], outputs + 32 * i);
     return BPR1CS_OK;
@@ -159,8 +150,7 @@ extern "C" int bpr1cs_msm(const uint8_t* scalars, const uint8_t* points, size_t 
         dev_h2d(d_p.p, points, 32 * n, st);
         dev_zero(fail.p, sizeof(int), st);
         launch(N, K_pip_prepare{d_s.p, d_p.p, pc.p, dig.p, fail.p, N}, st);
-        hipLaunchKernelGGL(k_pip_buckets, dim3(chunks, PIP_WINDOWS), dim3(256), 0, st, pc.p, dig.p, part.p, N, chunks);
-        HIPCHK(hipGetLastError());
+        launch_kernel(k_pip_buckets, dim3(chunks, PIP_WINDOWS), dim3(256), 0, st, pc.p, dig.p, part.p, N, chunks);
         launch(PIP_WINDOWS, K_ge_reduce{part.p, wsum.p, 1, PIP_WINDOWS * chunks, chunks}, st);
         launch(1, K_pip_horner{wsum.p, res.p}, st);
         launch(1, K_compress_one{res.p, d_out.p}, st);
@@ -250,9 +240,8 @@ extern "C" int bpr1cs_msm_fixed(const bpr1cs_gens* g, const uint32_t* bases, siz
             struct PinWipe { uint8_t* p; ~PinWipe() { memset(p, 0, 64); } } wipe{g->commit_pin};   // value and blinding are secrets: zeroed on every way out
             pin[0] = sc_load_raw(scalars);
             pin[1] = sc_load_raw(scalars + 32);
-            hipLaunchKernelGGL(k_commit_wave, dim3(1), dim3(64), 0, st, (const uint8_t*)g->tab.p, g->tc, (const sc*)pin, (const sc*)(pin + 1), g->commit_pin + 64, 1u, 1u);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(st));
+            launch_kernel(k_commit_wave, dim3(1), dim3(64), 0, st, g->tab.p, g->tc, pin, pin + 1, g->commit_pin + 64, 1u, 1u);
+            dev_sync(st);
             memcpy(out, g->commit_pin + 64, 32);
             return BPR1CS_OK;
         }
@@ -262,13 +251,11 @@ extern "C" int bpr1cs_msm_fixed(const bpr1cs_gens* g, const uint32_t* bases, siz
         DevBuf<sc> d((size_t)2 * B);
         DevBuf<uint8_t> d_out((size_t)B * 32);
         dev_h2d_async(d.p, h.data(), h.size() * sizeof(sc), st);
-#if !defined(BPR1CS_HOSTSIM)
+        bool wave = false;
         if (B <= 256) {   // a handful of commitments: a wavefront each (k_commit_wave), latency of ~6 additions instead of 2 x windows
-            hipLaunchKernelGGL(k_commit_wave, dim3(B), dim3(64), 0, st, (const uint8_t*)g->tab.p, g->tc, (const sc*)d.p, (const sc*)(d.p + B), d_out.p, B, 1u);
-            HIPCHK(hipGetLastError());
-        } else
-#endif
-        launch(B, K_commit_v{g->tab.p, g->tc, d.p, d.p + B, d_out.p, B, 1}, st);
+            wave = LAUNCH_WAVE_FORM(true, B, st, k_commit_wave, g->tab.p, g->tc, d.p, d.p + B, d_out.p, B, 1u);
+        }
+        if (!wave) launch(B, K_commit_v{g->tab.p, g->tc, d.p, d.p + B, d_out.p, B, 1}, st);
         dev_zero(d.p, d.bytes(), st);   // value and blinding are secrets
         dev_d2h(out, d_out.p, (size_t)B * 32, st);
         return BPR1CS_OK;
@@ -305,11 +292,7 @@ extern "C" int bpr1cs_msm_fixed(const bpr1cs_gens* g, const uint32_t* bases, siz
     DevBuf<ge> all(total * (size_t)B);
     size_t off = 0;
     for (size_t j = 0; j < njobs; j++) {
-#if defined(BPR1CS_HOSTSIM)
-        memcpy(all.p + off * B, parts[j].p, (size_t)plans[j].nchunks * B * sizeof(ge));
-#else
-        HIPCHK(hipMemcpyAsync(all.p + off * B, parts[j].p, (size_t)plans[j].nchunks * B * sizeof(ge), hipMemcpyDeviceToDevice, st));
-#endif
+        dev_d2d(all.p + off * B, parts[j].p, (size_t)plans[j].nchunks * B * sizeof(ge), st);
         off += plans[j].nchunks;
     }
     DevBuf<uint8_t> d_out((size_t)B * 32);

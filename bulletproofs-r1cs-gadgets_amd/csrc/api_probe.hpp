@@ -10,27 +10,23 @@ extern "C" int bpr1cs_device_rates(double seconds_each, double* mad_lane_ops_per
     return BPR1CS_OK;
 #else
     API_TRY
-    hipDeviceProp_t prop;
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    HIPCHK(hipGetDeviceProperties(&prop, dev));
-    const uint32_t blocks = (uint32_t)prop.multiProcessorCount * 8u, threads = 256;  // 8 wavefronts per SIMD
+    const uint32_t blocks = dev_cu_count() * 8u, threads = 256;  // 8 wavefronts per SIMD
+    if (!blocks) throw DevError{DEV_ERR_DEVICE};
     dev_stream_t st{};
     CallScope scope(st);
     DevBuf<uint32_t> out((size_t)blocks * threads);
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
+    struct Events {
+        dev_event_t e0{}, e1{};
+        ~Events() { dev_event_destroy(&e0); dev_event_destroy(&e1); }
+    } ev;
+    dev_event_create(&ev.e0, true);
+    dev_event_create(&ev.e1, true);
     auto timed = [&](int which, uint32_t iters) {
-        HIPCHK(hipEventRecord(e0, st));
-        if (which == 0) hipLaunchKernelGGL(k_probe_mad, dim3(blocks), dim3(threads), 0, st, out.p, iters);
-        else hipLaunchKernelGGL(k_probe_madd, dim3(blocks), dim3(threads), 0, st, out.p, iters);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(e1, st));
-        HIPCHK(hipEventSynchronize(e1));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        return (double)ms * 1e-3;
+        dev_event_record(ev.e0, st);
+        launch_kernel(which == 0 ? k_probe_mad : k_probe_madd, dim3(blocks), dim3(threads), 0, st, out.p, iters);
+        dev_event_record(ev.e1, st);
+        if (!dev_event_sync(ev.e1)) throw DevError{DEV_ERR_DEVICE};
+        return (double)dev_event_ms(ev.e0, ev.e1) * 1e-3;
     };
     double rate[2];
     for (int which = 0; which < 2; which++) {
@@ -42,8 +38,6 @@ extern "C" int bpr1cs_device_rates(double seconds_each, double* mad_lane_ops_per
         t = timed(which, (uint32_t)want);
         rate[which] = (double)blocks * threads * (double)want * (which == 0 ? 8.0 : 1.0) / t;
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     *mad_lane_ops_per_s = rate[0];
     *table_adds_per_s = rate[1];
     return BPR1CS_OK;

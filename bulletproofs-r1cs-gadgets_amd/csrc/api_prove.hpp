@@ -51,24 +51,17 @@ inline HostStage& host_stage() {
 }
 static void* host_stage_alloc(size_t n) {
     if (n == 0) n = 1;
-#if defined(BPR1CS_HOSTSIM)
-    return malloc(n);
-#else
     HostStage& hs = host_stage();
     std::lock_guard<std::mutex> lk(hs.mu);
     auto it = hs.cache.lower_bound(n);
     void* p = nullptr;
     size_t sz = n;
     if (it != hs.cache.end() && it->first <= 2 * n + 4096) { p = it->second; sz = it->first; hs.cache.erase(it); }
-    else HIPCHK(hipHostMalloc(&p, n, hipHostMallocDefault));
+    else p = dev_host_alloc(n);
     hs.live[p] = sz;
     return p;
-#endif
 }
 static void host_stage_free(void* p) {
-#if defined(BPR1CS_HOSTSIM)
-    free(p);
-#else
     if (!p) return;
     HostStage& hs = host_stage();
     std::lock_guard<std::mutex> lk(hs.mu);
@@ -76,17 +69,6 @@ static void host_stage_free(void* p) {
     if (it == hs.live.end()) return;
     hs.cache.insert({it->second, p});
     hs.live.erase(it);
-#endif
-}
-// compute units of the current device (k_rng_stream's capacity at one wavefront per SIMD is sized from it)
-static uint32_t dev_cu_count() {
-#if defined(BPR1CS_HOSTSIM)
-    return 256;
-#else
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;   // (0: no share)
-    return cus > 0 ? (uint32_t)cus : 0u;
-#endif
 }
 // diagnostic (include/bpr1cs.h, "Environment"): BPR1CS_DEBUG_JOBS prints host-side timestamps of the job pipeline to stderr
 static bool dbg_jobs() {
@@ -107,19 +89,14 @@ static void job_wait(bpr1cs_job* job) {
     // the heavy stream is shared with the NEXT job in flight: wait for this job's own completion event, and for the
     // whole stream only when the job failed before recording it
     if (job->ev_done) (void)dev_event_sync(job->ev_done);
-#if !defined(BPR1CS_HOSTSIM)
-    else if (job->st) (void)hipStreamSynchronize(job->st);
-    if (job->st2) (void)hipStreamSynchronize(job->st2);
-    if (job->st3) (void)hipStreamSynchronize(job->st3);
-#endif
+    else if (job->st) dev_sync_quiet(job->st);
+    if (job->st2) dev_sync_quiet(job->st2);
+    if (job->st3) dev_sync_quiet(job->st3);
 }
 static void job_release(bpr1cs_job* job) {
     if (!job) return;
     job_wait(job);
-#if !defined(BPR1CS_HOSTSIM)
-    for (auto e : job->pt.ev) (void)hipEventDestroy(e);
-    job->pt.ev.clear();
-#endif
+    job->pt.release();
     dev_event_t* evs[9] = {&job->ev_in, &job->ev_rng, &job->ev_wit, &job->ev_done, &job->ev_tail, &job->ev_head, &job->ev_rng_half, &job->ev_rng_half_h,
                            &job->ev_rng_red};
     for (auto e : evs) dev_event_destroy(e);
@@ -265,11 +242,7 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     PhaseTimer& pt = job->pt;
     MsmStats* stats = &job->msm;
     job->B = B; job->m = m;
-#if defined(BPR1CS_HOSTSIM)
-    dev_stream_t sl = st;
-#else
     dev_stream_t sl = job->st2;  // the latency-bound front of the job never touches the heavy stream
-#endif
     pt.mark(sl);
     DBG_JOB("begin: slot %u, %u proofs", slot, B);
 
@@ -315,14 +288,9 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
         dev_zero(Vcomp.p, Vcomp.bytes(), sl);   // (the caller has made the commitments - they are in its transcripts - and this call returns none)
     } else
     if (g->ct()) run_commit_ct(g, v_raw, vbl_raw, MSM_CANONICAL, m * B, Vcomp.p, B, m, sl, nullptr);   // (whatever the count: one kernel covers the contract)
-    else
-#if !defined(BPR1CS_HOSTSIM)
-    if ((uint64_t)m * B <= 256 && m * B > 0) {   // a handful of commitments in front of the transcript chain: a wavefront each (180 -> ~25 us for one proof)
-        hipLaunchKernelGGL(k_commit_wave, dim3(m * B), dim3(64), 0, sl, (const uint8_t*)g->tab.p, g->tc, (const sc*)v_raw, (const sc*)vbl_raw, Vcomp.p, B, m);
-        HIPCHK(hipGetLastError());
-    } else
-#endif
-    launch((uint64_t)m * B, K_commit_v{g->tab.p, g->tc, v_raw, vbl_raw, Vcomp.p, B, m}, sl);
+    // a handful of commitments in front of the transcript chain: a wavefront each (180 -> ~25 us for one proof)
+    else if (!LAUNCH_WAVE_FORM((uint64_t)m * B <= 256 && m * B > 0, m * B, sl, k_commit_wave, g->tab.p, g->tc, v_raw, vbl_raw, Vcomp.p, B, m))
+        launch((uint64_t)m * B, K_commit_v{g->tab.p, g->tc, v_raw, vbl_raw, Vcomp.p, B, m}, sl);
     DevBuf<strobe> tr(B);
     const bool shared = g->opts.shared_back.load() != 0;   // jobs in flight share W / the raw RNG output / the back-phase scratch
     DevBuf<sc> blind((size_t)8 * B), W;
@@ -404,26 +372,23 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
             kw.ptab = c->ptab.p; kw.perms = c->perms.p; kw.n_perms = c->n_perms; kw.pconst = c->pconst.p;
             kw.px = px.p; kw.pzf = pzf.p; kw.px_stride = c->px_stride;
         }
+        const dev_stream_t sw = job->st3;
+        dev_stream_wait(sw, job->ev_in);
+        if (shared) dev_stream_wait(sw, g->w_free_ev);
 #if defined(BPR1CS_HOSTSIM)
         (void)o_team;
-        launch(B, kw, st);
-        if (o_check) enqueue_witness_check(c, W.p, v_m.p, chk, B, st);
+        launch(B, kw, sw);   // (a lane per proof: the simulator has no teams)
 #else
         int T = o_team;
         if (c->n_perms && (uint32_t)T < c->macro_width + 2) T = 16;  // poseidon_team needs width + 2 lanes
         kw.prio = 2;  // above the co-resident MSM waves (default 0), below the RNG chain (3)
-        uint32_t blocks = (uint32_t)(((uint64_t)B * T + 63) / 64);
-        dev_stream_wait(job->st3, job->ev_in);
-        if (shared) dev_stream_wait(job->st3, g->w_free_ev);
-        if (T == 4) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_witness_team<4>), dim3(blocks), dim3(64), 0, job->st3, kw);
-        else if (T == 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_witness_team<8>), dim3(blocks), dim3(64), 0, job->st3, kw);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_witness_team<16>), dim3(blocks), dim3(64), 0, job->st3, kw);
-        HIPCHK(hipGetLastError());
-        if (o_check) enqueue_witness_check(c, W.p, v_m.p, chk, B, job->st3);
-        dev_event_create(&job->ev_wit);
-        dev_event_record(job->ev_wit, job->st3);
-        dev_stream_wait(st, job->ev_wit);
+        const dim3 blocks((uint32_t)(((uint64_t)B * T + 63) / 64));
+        launch_kernel(T == 4 ? k_witness_team<4> : T == 8 ? k_witness_team<8> : k_witness_team<16>, blocks, dim3(64), 0, sw, kw);
 #endif
+        if (o_check) enqueue_witness_check(c, W.p, v_m.p, chk, B, sw);
+        dev_event_create(&job->ev_wit);
+        dev_event_record(job->ev_wit, sw);
+        dev_stream_wait(st, job->ev_wit);
     }
     DBG_JOB("begin: front enqueued");
     // ---- P2: A_I1, A_O1, S1.  The sums of A_I1 and A_O1 need the wires only, so they are enqueued BEFORE the heavy stream
@@ -592,17 +557,15 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
         run_commit_ct(g, tsc.p, tsc.p + (size_t)5 * B, MSM_MONT, 5 * B, Tc.p, B, 0, st, stats);
         dev_zero(tsc.p, tsc.bytes(), st);   // (blindings)
     } else
-    launch_commit_T(K_commit_T{g->tab.p, g->tc, tco.p, blind.p, Tc.p, B}, B, st);
-    K_transcript_T ktt{tr.p, Tc.p, tco.p, blind.p, wvec + (size_t)3 * n * B, vbl_m.p, chal.p, txs.p, B, m, (uint64_t)N};
-    DevBuf<sc> t2b_pre;
-#if !defined(BPR1CS_HOSTSIM)
-    if (B <= FINISH_WAVE_MAX_PROOFS && m > 1) {
-        t2b_pre.alloc(B);
-        hipLaunchKernelGGL(k_dot_wave, dim3(B), dim3(64), 0, st, ktt.wV, ktt.vbl_m, t2b_pre.p, B, m);
-        HIPCHK(hipGetLastError());
-        ktt.t2b_pre = t2b_pre.p;
+    {
+        const K_commit_T kct{g->tab.p, g->tc, tco.p, blind.p, Tc.p, B};
+        if (!LAUNCH_WAVE_FORM(B <= FINISH_WAVE_MAX_PROOFS, 5u * B, st, k_commit_T_wave, kct)) launch((uint64_t)5 * B, kct, st);
     }
-#endif
+    K_transcript_T ktt{tr.p, Tc.p, tco.p, blind.p, wvec + (size_t)3 * n * B, vbl_m.p, chal.p, txs.p, B, m, (uint64_t)N};
+    const bool dot_wave = B <= FINISH_WAVE_MAX_PROOFS && m > 1;   // (otherwise K_transcript_T forms the dot product itself)
+    DevBuf<sc> t2b_pre;
+    if (dot_wave) t2b_pre.alloc(B);
+    if (LAUNCH_WAVE_FORM(dot_wave, B, st, k_dot_wave, ktt.wV, ktt.vbl_m, t2b_pre.p, B, m)) ktt.t2b_pre = t2b_pre.p;
     launch_transcript(B, ktt, st);
     DevBuf<sc> a((size_t)N * B), bb((size_t)N * B);
     launch((uint64_t)N * B, K_lr_eval{W.p, wvec, plo.p, phi.p, chal.p, a.p, bb.p, cG, cH, B, H, n}, st);
@@ -706,10 +669,8 @@ static int prove_job_end(bpr1cs_job* job, uint8_t* proofs_out, uint8_t* commitme
     DBG_JOB("end: waiting for slot %d", job->slot);
     if (!dev_event_sync(job->ev_done)) rc = BPR1CS_ERR_DEVICE;
     DBG_JOB("end: job of slot %d done", job->slot);
-#if !defined(BPR1CS_HOSTSIM)
-    (void)hipStreamSynchronize(job->st2);
-    (void)hipStreamSynchronize(job->st3);
-#endif
+    dev_sync_quiet(job->st2);
+    dev_sync_quiet(job->st3);
     if (rc == BPR1CS_OK) {
         memcpy(proofs_out, job->h_proofs, (size_t)job->B * job->plen);
         if (commitments_out && job->m) memcpy(commitments_out, job->h_comms, (size_t)job->B * job->m * 32);
@@ -904,9 +865,7 @@ static int prove_batch_impl(const bpr1cs_gens* g, const bpr1cs_circuit* c, const
             g->front[1].release();
             g->shared_front.release();
             circuit_cache_purge();   // (circuits nobody holds, with their per-handle tables)
-#if !defined(BPR1CS_HOSTSIM)
-            dev_pool().release_all();
-#endif
+            dev_release_cache();
             if (retried) {
                 // half of what just failed, for the rest of THIS call only; the remembered choice is dropped, so the next call sizes
                 // its jobs from the memory that is free then - a transient shortage (or a short last job) does not pin a small size

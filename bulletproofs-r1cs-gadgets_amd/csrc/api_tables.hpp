@@ -3,22 +3,8 @@
 #include "api_common.hpp"
 extern "C" {
 
-int bpr1cs_device_count(void) {
-#if defined(BPR1CS_HOSTSIM)
-    return 1;
-#else
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-#endif
-}
-int bpr1cs_set_device(int ordinal) {
-#if !defined(BPR1CS_HOSTSIM)
-    if (hipSetDevice(ordinal) != hipSuccess) return BPR1CS_ERR_NO_DEVICE;
-#endif
-    (void)ordinal;
-    return BPR1CS_OK;
-}
+int bpr1cs_device_count(void) { return dev_count(); }
+int bpr1cs_set_device(int ordinal) { return dev_set(ordinal) ? BPR1CS_OK : BPR1CS_ERR_NO_DEVICE; }
 int bpr1cs_circuit_macro_perms(const bpr1cs_circuit* c) { return c ? (int)c->n_perms : 0; }
 int bpr1cs_gens_set_option(bpr1cs_gens* g, int option, int value) {
     if (!g) return BPR1CS_ERR_INVALID_ARGUMENT;
@@ -48,9 +34,7 @@ int bpr1cs_gens_release_scratch(bpr1cs_gens* g) {
 }
 int bpr1cs_release_cached_memory(void) {
     circuit_cache_purge();   // cached circuits nobody holds (their device buffers go to the pool first)
-#if !defined(BPR1CS_HOSTSIM)
-    dev_pool().release_all();
-#endif
+    dev_release_cache();
     return BPR1CS_OK;
 }
 void bpr1cs_gens_destroy(bpr1cs_gens* g);
@@ -91,13 +75,11 @@ int bpr1cs_gens_create_opts(uint32_t cap, const int32_t* pairs, size_t n_pairs, 
 #endif
     }
     g->tc = tab_cfg((uint32_t)window_bits);
-#if !defined(BPR1CS_HOSTSIM)
-    HIPCHK(hipStreamCreate(&g->stream));
+    dev_stream_create(&g->stream);
     int prio_lo = 0, prio_hi = 0;
-    HIPCHK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));  // numerically lower = higher priority
+    dev_priority_range(&prio_lo, &prio_hi);  // numerically lower = higher priority
     for (int a = 0; a < 2; a++)
-        for (int b = 0; b < 3; b++) HIPCHK(hipStreamCreateWithPriority(&g->jstream[a][b], hipStreamNonBlocking, b == 0 ? prio_lo : prio_hi));
-#endif
+        for (int b = 0; b < 3; b++) dev_stream_create(&g->jstream[a][b], b == 0 ? prio_lo : prio_hi);
     dev_event_create(&g->w_free_ev);
     dev_event_create(&g->rng_free_ev);
     CallScope scope(g->stream);
@@ -154,11 +136,9 @@ void bpr1cs_gens_destroy(bpr1cs_gens* g) {
     dev_event_destroy(&g->w_free_ev);
     dev_event_destroy(&g->rng_free_ev);
     if (g->commit_pin) { host_stage_free(g->commit_pin); g->commit_pin = nullptr; }
-#if !defined(BPR1CS_HOSTSIM)
-    if (g->stream) (void)hipStreamDestroy(g->stream);
+    dev_stream_destroy(&g->stream);
     for (int a = 0; a < 2; a++)
-        for (int b = 0; b < 3; b++) if (g->jstream[a][b]) (void)hipStreamDestroy(g->jstream[a][b]);
-#endif
+        for (int b = 0; b < 3; b++) dev_stream_destroy(&g->jstream[a][b]);
     delete g;
 }
 uint32_t bpr1cs_gens_capacity(const bpr1cs_gens* g) { return g ? g->cap : 0; }

@@ -77,7 +77,8 @@ static void verify_front(VerifyCtx& v, const bpr1cs_gens* g, const bpr1cs_circui
     }
     sc* wc = v.wvec.p + (size_t)(3 * n + m + p) * B;
     // w_c += sum_k (column of public input k) x p_k; a non-canonical public input makes its proof malformed
-    if (p) launch_verify_public(K_verify_public{v.wvec.p + (size_t)(3 * n + m) * B, v.d_pub, wc, v.fail.p, B, p}, st);
+    const K_verify_public kpub{v.wvec.p + (size_t)(3 * n + m) * B, v.d_pub, wc, v.fail.p, B, p};
+    if (p && !LAUNCH_WAVE_FORM(B <= FINISH_WAVE_MAX_PROOFS, B, st, k_verify_public_wave, kpub)) launch(B, kpub, st);
     launch(B, K_verify_bscalars{v.chal.p, wc, v.delta.p, v.bsc.p, B}, st);
     v.P = 8 + m + 2 * lgN;
 }
@@ -115,8 +116,7 @@ static int verify_batch_once(const bpr1cs_gens* g, const bpr1cs_circuit* c, cons
         vtab.alloc((size_t)VB_MULT * T); vdig.alloc((size_t)VB_WORDS * T); vpart.alloc((size_t)VB_WINDOWS * B); pts.alloc(B);
         kp.vtab = vtab.p; kp.vdig = vdig.p;
         launch((uint64_t)T, kp, st);
-        hipLaunchKernelGGL(k_verify_win_wave, dim3(VB_WINDOWS * B), dim3(64), 0, st, (const ge_cached*)vtab.p, (const uint32_t*)vdig.p, vpart.p, B, v.P);
-        HIPCHK(hipGetLastError());
+        launch_kernel(k_verify_win_wave, dim3(VB_WINDOWS * B), dim3(64), 0, st, vtab.p, vdig.p, vpart.p, B, v.P);
         launch(B, K_ipa_vb_horner{vpart.p, pts.p, B, 1}, st);
         n_pts = 1;
     } else
@@ -126,7 +126,8 @@ static int verify_batch_once(const bpr1cs_gens* g, const bpr1cs_circuit* c, cons
         kp.out = pts.p;
         launch((uint64_t)v.P * B, kp, st);
     }
-    launch_verify_finish(K_verify_finish{g->tab.p, g->tc, partial.p, pts.p, v.bsc.p, v.fail.p, ok.p, B, plan.nchunks, n_pts}, st);
+    const K_verify_finish kf{g->tab.p, g->tc, partial.p, pts.p, v.bsc.p, v.fail.p, ok.p, B, plan.nchunks, n_pts};
+    if (!LAUNCH_WAVE_FORM(B <= FINISH_WAVE_MAX_PROOFS, B, st, k_verify_finish_wave, kf)) launch(B, kf, st);
     dev_d2h(ok_out, ok.p, sizeof(int) * B, st);
     stats.collect();
     return BPR1CS_OK;
@@ -236,13 +237,7 @@ static uint32_t combine_grouped_wgs(uint64_t rows, uint64_t NG) {
 }
 static void launch_combine_ranges(uint32_t rows, const K_combine_scalars_ranges& f, dev_stream_t st) {
     const uint32_t wgs = combine_grouped_wgs(rows, f.R);
-    if (!wgs) return;
-#if !defined(BPR1CS_HOSTSIM)
-    hipLaunchKernelGGL(k_combine_scalars_range_wave, dim3(wgs), dim3(64), 0, st, f, rows * f.R);
-    HIPCHK(hipGetLastError());
-#else
-    launch((uint64_t)rows * f.R, f, st);
-#endif
+    if (wgs) LAUNCH_WAVE_ALWAYS(wgs, st, k_combine_scalars_range_wave, (uint64_t)rows * f.R, f, f, rows * f.R);
 }
 #if defined(BPR1CS_HOSTSIM)
 // Simulator only (never part of libbpr1cs_hip.so): the launch geometry above for a shape no test can afford to run - *wgs = workgroups
@@ -310,12 +305,14 @@ static int verify_batch_bisect_once(const bpr1cs_gens* g, const bpr1cs_circuit* 
             const uint32_t *lo = d_rng.p + off, *hi = d_rng.p + R + off, *par = d_rng.p + 2 * (size_t)R + off;
             launch_combine_ranges(2 * N, K_combine_scalars_ranges{v.gh.p, k.rho.p, v.fail.p, lo, hi, k.cgh.p, B, cnt}, st);
             launch_combine_ranges(2, K_combine_scalars_ranges{v.bsc.p, k.rho.p, v.fail.p, lo, hi, k.cb.p, B, cnt}, st);
-            launch_range_points(K_range_points{k.pts.p, v.fail.p, lo, hi, rpts.p, B, v.P}, cnt, st);
+            const K_range_points krp{k.pts.p, v.fail.p, lo, hi, rpts.p, B, v.P};   // (a wavefront per range whatever their number: a range is up to G x P points)
+            LAUNCH_WAVE_ALWAYS(cnt, st, k_range_points_wave, cnt, krp, krp);
             MsmPlan plan;
             MsmSeg sg{k.cgh.p, N, N, N, 0, baseG, 0}, sh{k.cgh.p + (size_t)N * cnt, N, N, N, 0, baseH, 0};
             run_msm(g, sg, sh, cnt, partial, plan, st, &stats);
-            launch_range_finish(K_range_finish{g->tab.p, g->tc, partial.p, rpts.p, k.cb.p, parent, par, out.p + off, out.p + R + off,
-                                               d_zero.p + off, d_zero.p + R + off, cnt, plan.nchunks}, st);
+            const K_range_finish krf{g->tab.p, g->tc, partial.p, rpts.p, k.cb.p, parent, par, out.p + off, out.p + R + off,
+                                     d_zero.p + off, d_zero.p + R + off, cnt, plan.nchunks};
+            if (!LAUNCH_WAVE_FORM(cnt <= FINISH_WAVE_MAX_PROOFS, cnt, st, k_range_finish_wave, krf)) launch(cnt, krf, st);
         }
         zero.resize((size_t)2 * R);
         dev_d2h(zero.data(), d_zero.p, sizeof(int) * (depth ? 2 * (size_t)R : R), st);
@@ -438,9 +435,7 @@ static int with_scratch_retry(const bpr1cs_gens* g, F&& once) {
     int rc = once();
     if (rc == BPR1CS_ERR_OUT_OF_MEMORY && g && g->in_flight.load() == 0) {
         g->arena.release(); g->front[0].release(); g->front[1].release(); g->shared_front.release();
-#if !defined(BPR1CS_HOSTSIM)
-        dev_pool().release_all();
-#endif
+        dev_release_cache();
         rc = once();
     }
     return rc;

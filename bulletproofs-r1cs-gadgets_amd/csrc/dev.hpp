@@ -12,7 +12,6 @@
 #include <stdlib.h>
 #include <string.h>
 #include <stdio.h>
-#include <typeinfo>
 #include "hd.hpp"
 
 #include <vector>
@@ -43,6 +42,18 @@ inline void dev_d2h(void* h, const void* d, size_t n, dev_stream_t) { memcpy(h, 
 inline void dev_zero(void* d, size_t n, dev_stream_t) { memset(d, 0, n); }
 inline void dev_d2d(void* d, const void* s, size_t n, dev_stream_t) { memcpy(d, s, n); }
 inline void dev_sync(dev_stream_t) {}
+inline void dev_sync_quiet(dev_stream_t) {}
+inline void dev_stream_create(dev_stream_t* s) { *s = 0; }
+inline void dev_stream_create(dev_stream_t* s, int /* priority */) { *s = 0; }
+inline void dev_stream_destroy(dev_stream_t* s) { *s = 0; }
+inline void dev_priority_range(int* lo, int* hi) { *lo = *hi = 0; }
+inline void dev_release_cache() {}
+inline int dev_count() { return 1; }
+inline bool dev_set(int) { return true; }
+inline int dev_current() { return 0; }
+inline uint32_t dev_cu_count() { return 256; }
+inline void* dev_host_alloc(size_t n) { return malloc(n); }
+inline void dev_host_free(void* p) { free(p); }
 // events / cross-stream order: the simulator is synchronous, so these are no-ops
 typedef int dev_event_t;
 inline void dev_event_create(dev_event_t* e, bool = false) { *e = 1; }
@@ -63,6 +74,9 @@ template <class F>
 inline void launch_wave(uint64_t n, const F& f, dev_stream_t s) { launch(n, f, s); }
 template <class F>
 inline void launch_transcript(uint64_t n, const F& f, dev_stream_t s) { launch(n, f, s); }
+// (no wavefronts here: always the caller's lane functor; the kernel's name is swallowed - this build never sees kernels_hip.hpp)
+#define LAUNCH_WAVE_FORM(cond, grid, st, kernel, ...) ((void)(cond), false)
+#define LAUNCH_WAVE_ALWAYS(grid, st, kernel, n, f, ...) launch(n, f, st)
 #else
 #include <hip/hip_runtime.h>
 typedef hipStream_t dev_stream_t;
@@ -174,6 +188,34 @@ inline void dev_d2h(void* h, const void* d, size_t n, dev_stream_t s) {
 inline void dev_zero(void* d, size_t n, dev_stream_t s) { HIPCHK(hipMemsetAsync(d, 0, n, s)); }
 inline void dev_d2d(void* d, const void* src, size_t n, dev_stream_t s) { HIPCHK(hipMemcpyAsync(d, src, n, hipMemcpyDeviceToDevice, s)); }
 inline void dev_sync(dev_stream_t s) { HIPCHK(hipStreamSynchronize(s)); }
+inline void dev_sync_quiet(dev_stream_t s) { (void)hipStreamSynchronize(s); }   // (ends of jobs and calls, destructors: never throws)
+inline void dev_stream_create(dev_stream_t* s) { HIPCHK(hipStreamCreate(s)); }
+inline void dev_stream_create(dev_stream_t* s, int priority) { HIPCHK(hipStreamCreateWithPriority(s, hipStreamNonBlocking, priority)); }
+inline void dev_stream_destroy(dev_stream_t* s) { if (*s) { (void)hipStreamDestroy(*s); *s = nullptr; } }
+inline void dev_priority_range(int* lo, int* hi) { HIPCHK(hipDeviceGetStreamPriorityRange(lo, hi)); }  // numerically lower = higher priority
+inline void dev_release_cache() { dev_pool().release_all(); }
+inline int dev_count() {
+    int n = 0;
+    return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
+}
+inline bool dev_set(int ordinal) { return hipSetDevice(ordinal) == hipSuccess; }
+inline int dev_current() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
+    return dev;
+}
+// compute units of the current device (0: unknown)
+inline uint32_t dev_cu_count() {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    return cus > 0 ? (uint32_t)cus : 0u;
+}
+inline void* dev_host_alloc(size_t n) {   // pinned
+    void* p = nullptr;
+    HIPCHK(hipHostMalloc(&p, n, hipHostMallocDefault));
+    return p;
+}
+inline void dev_host_free(void* p) { (void)hipHostFree(p); }
 typedef hipEvent_t dev_event_t;
 inline void dev_event_create(dev_event_t* e, bool timing = false) {
     if (timing) HIPCHK(hipEventCreate(e));
@@ -183,6 +225,11 @@ inline void dev_event_record(dev_event_t e, dev_stream_t s) { HIPCHK(hipEventRec
 inline void dev_stream_wait(dev_stream_t s, dev_event_t e) { HIPCHK(hipStreamWaitEvent(s, e, 0)); }
 inline bool dev_event_sync(dev_event_t e) { return hipEventSynchronize(e) == hipSuccess; }
 inline void dev_event_destroy(dev_event_t* e) { if (*e) { (void)hipEventDestroy(*e); *e = nullptr; } }
+inline float dev_event_ms(dev_event_t a, dev_event_t b) {   // timing events, `b` complete (dev_event_sync); 0 when the runtime has no time for them
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); ms = 0; }
+    return ms;
+}
 inline void dev_d2h_async(void* h, const void* d, size_t n, dev_stream_t s) { HIPCHK(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, s)); }
 inline void dev_h2d_async(void* d, const void* h, size_t n, dev_stream_t s) { HIPCHK(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, s)); }
 // device memory a new allocation can draw on: what the driver reports free plus what the allocator's cache holds
@@ -191,6 +238,26 @@ inline size_t dev_free_memory() {
     if (hipMemGetInfo(&mfree, &mtotal) != hipSuccess) { (void)hipGetLastError(); mfree = 0; }
     return mfree + dev_pool().cached_bytes();
 }
+
+// EVERY kernel launch of the product goes through here: the launch, its error check, and the BPR1CS_DEBUG_SYNC diagnostic
+// (include/bpr1cs.h, "Environment": synchronise after every launch and name it).  The arguments are forwarded to the kernel's own
+// parameter list, so a call site converts implicitly exactly as a direct launch would.
+template <class... P, class... A>
+inline void launch_kernel(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, dev_stream_t s, A&&... args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, static_cast<A&&>(args)...);
+    HIPCHK(hipGetLastError());
+    static const bool dbg = getenv("BPR1CS_DEBUG_SYNC") != nullptr;
+    if (dbg) {
+        const char* name = hipKernelNameRefByPtr((const void*)kernel, s);
+        fprintf(stderr, "bpr1cs: launched %s grid=%u,%u block=%u\n", name ? name : "?", grid.x, grid.y, block.x);
+        HIPCHK(hipStreamSynchronize(s));
+    }
+}
+// "This wavefront-per-output kernel (one 64-lane workgroup per output, `grid` of them) when `cond` holds": true when it launched;
+// otherwise the caller runs its lane functor - if (!LAUNCH_WAVE_FORM(cond, grid, st, k_x_wave, args...)) launch(n, f, st);
+#define LAUNCH_WAVE_FORM(cond, grid, st, kernel, ...) ((cond) ? (launch_kernel(kernel, dim3(grid), dim3(64), 0, st, __VA_ARGS__), true) : false)
+// ... and the wavefront kernel whatever the size: lane functor `f` over `n` outputs in the simulator only (here its kernel is never built)
+#define LAUNCH_WAVE_ALWAYS(grid, st, kernel, n, f, ...) launch_kernel(kernel, dim3(grid), dim3(64), 0, st, __VA_ARGS__)
 
 template <class F>
 __global__ void __launch_bounds__(256) k_functor(F f, uint32_t n) {
@@ -203,14 +270,7 @@ template <class F>
 inline void launch(uint64_t n, const F& f, dev_stream_t s) {
     if (n == 0) return;
     if (n > 0xffffffffull) throw DevError{DEV_ERR_INVALID_ARGUMENT};  // entry points bound their batch so that this cannot happen
-    uint32_t blocks = (uint32_t)((n + 255) / 256);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_functor<F>), dim3(blocks), dim3(256), 0, s, f, (uint32_t)n);
-    HIPCHK(hipGetLastError());
-    static const bool dbg = getenv("BPR1CS_DEBUG_SYNC") != nullptr;
-    if (dbg) {
-        fprintf(stderr, "bpr1cs: launched %s n=%llu\n", typeid(F).name(), (unsigned long long)n);
-        HIPCHK(hipStreamSynchronize(s));
-    }
+    launch_kernel(k_functor<F>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, f, (uint32_t)n);
 }
 // One wavefront per workgroup: the unit the dispatcher places (and retires) is a single wave, so a wave that
 // shares its SIMD with a co-running latency-bound kernel never pins three idle sibling waves' registers.
@@ -223,14 +283,7 @@ template <class F>
 inline void launch_wave(uint64_t n, const F& f, dev_stream_t s) {
     if (n == 0) return;
     if (n > 0xffffffffull) throw DevError{DEV_ERR_INVALID_ARGUMENT};
-    uint32_t blocks = (uint32_t)((n + 63) / 64);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_functor_wave<F>), dim3(blocks), dim3(64), 0, s, f, (uint32_t)n);
-    HIPCHK(hipGetLastError());
-    static const bool dbg = getenv("BPR1CS_DEBUG_SYNC") != nullptr;
-    if (dbg) {
-        fprintf(stderr, "bpr1cs: launched (wave) %s n=%llu\n", typeid(F).name(), (unsigned long long)n);
-        HIPCHK(hipStreamSynchronize(s));
-    }
+    launch_kernel(k_functor_wave<F>, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, s, f, (uint32_t)n);
 }
 // Transcript kernels of a handful of proofs: one 32-lane workgroup per transcript, every lane running the functor for the SAME
 // proof (identical loads, identical stores) so that the permutations inside - the whole cost of such a kernel - can be split
@@ -245,13 +298,7 @@ template <class F>
 inline void launch_transcript(uint64_t n, const F& f, dev_stream_t s) {
     if (n == 0) return;
     if (n > LOCKSTEP_MAX_PROOFS) { launch(n, f, s); return; }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_functor_lockstep<F>), dim3((uint32_t)n), dim3(32), 0, s, f, (uint32_t)n);
-    HIPCHK(hipGetLastError());
-    static const bool dbg = getenv("BPR1CS_DEBUG_SYNC") != nullptr;
-    if (dbg) {
-        fprintf(stderr, "bpr1cs: launched (lockstep) %s n=%llu\n", typeid(F).name(), (unsigned long long)n);
-        HIPCHK(hipStreamSynchronize(s));
-    }
+    launch_kernel(k_functor_lockstep<F>, dim3((uint32_t)n), dim3(32), 0, s, f, (uint32_t)n);
 }
 #endif
 

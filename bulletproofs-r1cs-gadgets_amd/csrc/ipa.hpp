@@ -276,7 +276,7 @@ static IpaEnd enqueue_ipa(const IpaIO& io, dev_stream_t st, MsmStats* stats) {
                         L.geo = mg;
                     }
                     L.wg_end[0] = M * L.nbk; L.wg_end[1] = 2 * M * L.nbk;
-                    launch_msm_kernel(g, L, st, stats, (uint64_t)2 * per_side * B, (uint64_t)2 * per_side * B * g->tc.windows);
+                    launch_msm_kernel(L, st, stats, (uint64_t)2 * per_side * B, (uint64_t)2 * per_side * B * g->tc.windows);
                     // the unit term: one table addition per output
                     if (unit) launch((uint64_t)2 * M * B, K_ipa_fold_unit{g->tab.p, g->tc, GHp, B, M, baseG, baseH}, st);
                 }

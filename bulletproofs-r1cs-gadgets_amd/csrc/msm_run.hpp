@@ -3,26 +3,24 @@
 #include "api_common.hpp"
 // ---------------------------------------------------------------- timing
 struct PhaseTimer {
-#if defined(BPR1CS_HOSTSIM)
-    void mark(dev_stream_t) {}
-    void finish(float*) {}
-#else
-    std::vector<hipEvent_t> ev;
+    std::vector<dev_event_t> ev;
     void mark(dev_stream_t s) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        HIPCHK(hipEventRecord(e, s));
+        dev_event_t e;
+        dev_event_create(&e, true);
         ev.push_back(e);
+        dev_event_record(e, s);
     }
     void finish(float* out) {  // out[0] total, out[1..] consecutive phases
-        if (ev.size() < 2) return;
-        HIPCHK(hipEventSynchronize(ev.back()));
-        HIPCHK(hipEventElapsedTime(&out[0], ev.front(), ev.back()));
-        for (size_t i = 1; i < ev.size() && i < 6; i++) HIPCHK(hipEventElapsedTime(&out[i], ev[i - 1], ev[i]));
-        for (auto e : ev) (void)hipEventDestroy(e);
+        if (ev.size() >= 2 && dev_event_sync(ev.back())) {
+            out[0] = dev_event_ms(ev.front(), ev.back());
+            for (size_t i = 1; i < ev.size() && i < 6; i++) out[i] = dev_event_ms(ev[i - 1], ev[i]);
+        }
+        release();
+    }
+    void release() {
+        for (auto& e : ev) dev_event_destroy(&e);
         ev.clear();
     }
-#endif
 };
 
 static uint32_t pick_chunks(uint64_t items, uint32_t B, uint32_t target_threads, uint32_t& chunk) {
@@ -71,14 +69,7 @@ static const uint32_t MSM_LANE_PATH_MAX_PROOFS = 64;
 static const uint32_t FINISH_WAVE_MAX_PROOFS = 64;
 static const uint32_t MSM_WAVE_REDUCE_MAX_CHUNK = 2;    // k_msm_small_wave (first reduction level inside the wavefront) while a lane sums at most this many terms (see run_msm_multi)
 static void launch_sum_partials(uint64_t outputs, const K_sum_partials& f, dev_stream_t st) {
-#if !defined(BPR1CS_HOSTSIM)
-    if (outputs <= 1024 && f.C >= 8) {
-        hipLaunchKernelGGL(k_sum_partials_wave, dim3((uint32_t)outputs), dim3(64), 0, st, f);
-        HIPCHK(hipGetLastError());
-        return;
-    }
-#endif
-    launch(outputs, f, st);
+    if (!LAUNCH_WAVE_FORM(outputs <= 1024 && f.C >= 8, (uint32_t)outputs, st, k_sum_partials_wave, f)) launch(outputs, f, st);
 }
 static void launch_wipe(const K_wipe& f, dev_stream_t st) {
     uint64_t total = 0;
@@ -91,95 +82,21 @@ static void launch_assemble(const K_assemble& f, dev_stream_t st) {
     if (f.B <= 1024) launch((uint64_t)(13 + 2 * f.lgN) * f.B, K_assemble_el{f}, st);
     else launch(f.B, f, st);
 }
-static void launch_commit_T(const K_commit_T& f, uint32_t B, dev_stream_t st) {
-#if !defined(BPR1CS_HOSTSIM)
-    if (B <= FINISH_WAVE_MAX_PROOFS) {
-        hipLaunchKernelGGL(k_commit_T_wave, dim3(5u * B), dim3(64), 0, st, f);
-        HIPCHK(hipGetLastError());
-        return;
-    }
-#endif
-    launch((uint64_t)5 * B, f, st);
-}
+// (K_commit_T, the verifier's per-proof and per-range kernels: the same threshold, at their one call site each)
 static void launch_pow_tables(const K_pow_tables& f, uint32_t B, dev_stream_t st) {
-#if !defined(BPR1CS_HOSTSIM)
-    if (B <= FINISH_WAVE_MAX_PROOFS) {
-        hipLaunchKernelGGL(k_pow_tables_wave, dim3(3u * B), dim3(64), 0, st, f);
-        HIPCHK(hipGetLastError());
-        return;
-    }
-#endif
-    launch((uint64_t)3 * B, f, st);
-}
-// the verifier's per-proof and per-range kernels: a wavefront per output for a handful of outputs, a lane per output above
-static void launch_verify_public(const K_verify_public& f, dev_stream_t st) {
-#if !defined(BPR1CS_HOSTSIM)
-    if (f.B <= FINISH_WAVE_MAX_PROOFS) {
-        hipLaunchKernelGGL(k_verify_public_wave, dim3(f.B), dim3(64), 0, st, f);
-        HIPCHK(hipGetLastError());
-        return;
-    }
-#endif
-    launch(f.B, f, st);
-}
-static void launch_verify_finish(const K_verify_finish& f, dev_stream_t st) {
-#if !defined(BPR1CS_HOSTSIM)
-    if (f.B <= FINISH_WAVE_MAX_PROOFS) {
-        hipLaunchKernelGGL(k_verify_finish_wave, dim3(f.B), dim3(64), 0, st, f);
-        HIPCHK(hipGetLastError());
-        return;
-    }
-#endif
-    launch(f.B, f, st);
-}
-static void launch_range_points(const K_range_points& f, uint32_t R, dev_stream_t st) {   // (a wavefront per range whatever R: a range is up to G x P points)
-#if !defined(BPR1CS_HOSTSIM)
-    hipLaunchKernelGGL(k_range_points_wave, dim3(R), dim3(64), 0, st, f);
-    HIPCHK(hipGetLastError());
-#else
-    launch(R, f, st);
-#endif
-}
-static void launch_range_finish(const K_range_finish& f, dev_stream_t st) {
-#if !defined(BPR1CS_HOSTSIM)
-    if (f.R <= FINISH_WAVE_MAX_PROOFS) {
-        hipLaunchKernelGGL(k_range_finish_wave, dim3(f.R), dim3(64), 0, st, f);
-        HIPCHK(hipGetLastError());
-        return;
-    }
-#endif
-    launch(f.R, f, st);
+    if (!LAUNCH_WAVE_FORM(B <= FINISH_WAVE_MAX_PROOFS, 3u * B, st, k_pow_tables_wave, f)) launch((uint64_t)3 * B, f, st);
 }
 static void launch_finish(const K_msm_finish& f, uint32_t B, dev_stream_t st) {
-#if !defined(BPR1CS_HOSTSIM)
-    if (B <= FINISH_WAVE_MAX_PROOFS && !f.extra_pt) {
-        hipLaunchKernelGGL(k_finish_wave, dim3(B), dim3(64), 0, st, f, f, f, B);
-        HIPCHK(hipGetLastError());
-        return;
-    }
-#endif
-    launch(B, f, st);
+    if (!LAUNCH_WAVE_FORM(B <= FINISH_WAVE_MAX_PROOFS && !f.extra_pt, B, st, k_finish_wave, f, f, f, B)) launch(B, f, st);
 }
 static void launch_finish_pair(const K_msm_finish& a, const K_msm_finish& b, uint32_t B, dev_stream_t st) {
-#if !defined(BPR1CS_HOSTSIM)
-    if (B <= FINISH_WAVE_MAX_PROOFS && !a.extra_pt && !b.extra_pt) {
-        hipLaunchKernelGGL(k_finish_wave, dim3(2 * B), dim3(64), 0, st, a, b, b, B);
-        HIPCHK(hipGetLastError());
-        return;
-    }
-#endif
-    launch((uint64_t)2 * B, K_pair<K_msm_finish>{a, b, B}, st);
+    if (!LAUNCH_WAVE_FORM(B <= FINISH_WAVE_MAX_PROOFS && !a.extra_pt && !b.extra_pt, 2 * B, st, k_finish_wave, a, b, b, B))
+        launch((uint64_t)2 * B, K_pair<K_msm_finish>{a, b, B}, st);
 }
 // A_I, A_O and S of a job of a few proofs: the three finishes (each a lone wavefront per proof: a butterfly and a compression, ~0.1 ms)
 // side by side in one launch instead of one after the other
 static void launch_finish_triple(const K_msm_finish& a, const K_msm_finish& b, const K_msm_finish& c, uint32_t B, dev_stream_t st) {
-#if !defined(BPR1CS_HOSTSIM)
-    if (B <= FINISH_WAVE_MAX_PROOFS && !a.extra_pt && !b.extra_pt && !c.extra_pt) {
-        hipLaunchKernelGGL(k_finish_wave, dim3(3 * B), dim3(64), 0, st, a, b, c, B);
-        HIPCHK(hipGetLastError());
-        return;
-    }
-#endif
+    if (LAUNCH_WAVE_FORM(B <= FINISH_WAVE_MAX_PROOFS && !a.extra_pt && !b.extra_pt && !c.extra_pt, 3 * B, st, k_finish_wave, a, b, c, B)) return;
     launch_finish_pair(a, b, B, st);
     launch_finish(c, B, st);
 }
@@ -189,29 +106,33 @@ static void launch_finish_triple(const K_msm_finish& a, const K_msm_finish& b, c
 struct MsmStats {
     double ms = 0;
     uint64_t launches = 0, terms = 0, adds = 0;  // terms = scalar*point products (summed over the batch); adds = table additions (terms x windows of their table)
-#if !defined(BPR1CS_HOSTSIM)
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-    hipEvent_t get() {
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        return e;
-    }
-    ~MsmStats() {
-        for (auto& p : ev) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-    }
-#endif
-    void collect() {  // after the stream has drained
-#if !defined(BPR1CS_HOSTSIM)
-        for (auto& p : ev) {
-            float t = 0;
-            if (hipEventSynchronize(p.second) == hipSuccess && hipEventElapsedTime(&t, p.first, p.second) == hipSuccess) ms += t;
-            (void)hipEventDestroy(p.first);
-            (void)hipEventDestroy(p.second);
-        }
+    std::vector<std::pair<dev_event_t, dev_event_t>> ev;
+    ~MsmStats() { release(); }
+    void release() {
+        for (auto& p : ev) { dev_event_destroy(&p.first); dev_event_destroy(&p.second); }
         ev.clear();
-#endif
+    }
+    void collect() {  // after the stream has drained
+        for (auto& p : ev)
+            if (dev_event_sync(p.second)) ms += dev_event_ms(p.first, p.second);
+        release();
     }
 };
+// one launch of the dominant kernel (`body` launches it), timed on its own stream by an event pair when `stats` is given
+template <class Body>
+static void msm_timed_launch(MsmStats* stats, dev_stream_t st, uint64_t terms, uint64_t adds, const Body& body) {
+    if (!stats) { body(); return; }
+    stats->ev.emplace_back();
+    std::pair<dev_event_t, dev_event_t>& e = stats->ev.back();
+    dev_event_create(&e.first, true);
+    dev_event_create(&e.second, true);
+    dev_event_record(e.first, st);
+    body();
+    dev_event_record(e.second, st);
+    stats->launches++;
+    stats->terms += terms;
+    stats->adds += adds;
+}
 
 // Launch geometry: many more workgroups than the chip holds at once (g_msm_target_threads / 64 >> 16 per CU), so
 // that the hardware dispatcher load-balances them - a launch of exactly one resident set makes every workgroup
@@ -219,43 +140,49 @@ struct MsmStats {
 // sums share one launch (k_msm_fixed2).  The chunk partials are folded `MSM_REDUCE_GROUP` at a time (twice when
 // there are many) before the per-proof finish kernel, which then adds at most MSM_REDUCE_GROUP points.
 static const uint32_t MSM_REDUCE_GROUP = 16;
-// a small job's levels: 64 at a time by a wavefront's butterfly (k_ge_reduce_wave); the CPU simulator's functor adds them serially
+// a small job's levels: 64 at a time by a wavefront's butterfly (k_ge_reduce_wave); the CPU simulator's functor adds them serially,
+// and it has no wavefronts for the first level either (k_msm_small_wave: its functor writes one sum per chunk)
 #if defined(BPR1CS_HOSTSIM)
 static const uint32_t SMALL_REDUCE_GROUP = 16;
 #else
 static const uint32_t SMALL_REDUCE_GROUP = 64;
 #endif
+static const bool SMALL_IN_WAVE = SMALL_REDUCE_GROUP == 64;   // (a build folds by wavefronts in both places or in neither)
+// The two wavefront kernels of a small job, for one request or for two of the same shape (`b` / in[1] null: one) in ONE launch;
+// the simulator runs the lane functor once per member.
+static void launch_msm_small_pair(const K_msm_fixed_small& a, const K_msm_fixed_small* b, uint32_t groups, dev_stream_t st) {
+#if defined(BPR1CS_HOSTSIM)
+    (void)groups;
+    launch_wave((uint64_t)a.nchunks * a.B, a, st);
+    if (b) launch_wave((uint64_t)b->nchunks * b->B, *b, st);
+#else
+    launch_kernel(k_msm_small_wave, dim3((b ? 2u : 1u) * groups * a.B), dim3(64), 0, st, a, b ? *b : a, groups);
+#endif
+}
+static void launch_ge_reduce_pair(const ge* const in[2], ge* const out[2], uint32_t B, uint32_t in_cnt, uint32_t out_cnt, dev_stream_t st) {
+#if defined(BPR1CS_HOSTSIM)
+    for (uint32_t u = 0; u < (in[1] ? 2u : 1u); u++) launch((uint64_t)out_cnt * B, K_ge_reduce{in[u], out[u], B, in_cnt, SMALL_REDUCE_GROUP}, st);
+#else
+    launch_kernel(k_ge_reduce_wave, dim3((in[1] ? 2u : 1u) * out_cnt * B), dim3(64), 0, st, in[0], out[0], in[1], out[1], B, in_cnt, out_cnt);
+#endif
+}
 // one launch of the dominant kernel, HIP-event timed on its own stream when `stats` is given; `terms` = scalar*point
 // products of the launch summed over the batch (every launch of k_msm_fixed2 goes through here, so that bench.py's roofline
 // object describes the whole kernel: the commit sums, L_k / R_k of the un-folded rounds AND the folded generators).
 // The simulator runs the same body lane by lane (msm_fixed2_sim).
-static void launch_msm_kernel(const bpr1cs_gens* g, MsmLaunch& L, dev_stream_t st, MsmStats* stats, uint64_t terms, uint64_t adds) {
+static void launch_msm_kernel(MsmLaunch& L, dev_stream_t st, MsmStats* stats, uint64_t terms, uint64_t adds) {
     L.nwg = (L.wg_end[L.njobs - 1] + 7u) & ~7u;  // a multiple of 8 keeps the XCD-aware remap on
     L.max_windows = 0;
     for (uint32_t r = 0; r < L.njobs; r++) L.max_windows = std::max(L.max_windows, L.job[r].tc.windows);
+    msm_timed_launch(stats, st, terms, adds, [&] {
 #if defined(BPR1CS_HOSTSIM)
-    (void)g; (void)st;
-    msm_trace().fixed2_launches++;
-    MSM_TRACE_F2(MSM_TR_GRID, L.nwg);
-    msm_fixed2_sim(L);
-    if (stats) { stats->launches++; stats->terms += terms; stats->adds += adds; }
+        msm_trace().fixed2_launches++;
+        MSM_TRACE_F2(MSM_TR_GRID, L.nwg);
+        msm_fixed2_sim(L);
 #else
-    hipEvent_t e0{}, e1{};
-    if (stats) {
-        e0 = stats->get(); e1 = stats->get();
-        stats->ev.push_back({e0, e1});
-        HIPCHK(hipEventRecord(e0, st));
-    }
-    const size_t lds = (size_t)2 * L.max_windows * 64 * sizeof(uint16_t);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_msm_fixed2<3>), dim3(L.nwg), dim3(64), lds, st, L);
-    HIPCHK(hipGetLastError());
-    if (stats) {
-        HIPCHK(hipEventRecord(e1, st));
-        stats->launches++;
-        stats->terms += terms;
-        stats->adds += adds;
-    }
+        launch_kernel(k_msm_fixed2<3>, dim3(L.nwg), dim3(64), (size_t)2 * L.max_windows * 64 * sizeof(uint16_t), st, L);
 #endif
+    });
 }
 // one launch of k_msm_fixed_ct (BPR1CS_OPT_SECRET_INDEPENDENT): same geometry, the narrow table set; counted in the same statistics
 static void launch_msm_ct_kernel(MsmLaunch& L, dev_stream_t st, MsmStats* stats, uint64_t terms, uint64_t adds) {
@@ -264,28 +191,15 @@ static void launch_msm_ct_kernel(MsmLaunch& L, dev_stream_t st, MsmStats* stats,
     for (uint32_t r = 0; r < L.njobs; r++)   // the kernel's digit buffer is sized for the narrow set, and it takes stored scalars only
         if (L.job[r].tc.windows != MSM_CT_WINDOWS || L.job[r].interleave || L.job[r].seg[0].geo || L.job[r].seg[1].geo ||
             L.job[r].seg[0].mont > MSM_MONT || L.job[r].seg[1].mont > MSM_MONT) throw DevError{BPR1CS_ERR_INVALID_ARGUMENT};
+    msm_timed_launch(stats, st, terms, adds, [&] {
 #if defined(BPR1CS_HOSTSIM)
-    (void)st;
-    msm_trace().ct_launches++;
-    MSM_TRACE(MSM_TR_GRID, L.nwg);
-    msm_fixed_ct_sim(L);
-    if (stats) { stats->launches++; stats->terms += terms; stats->adds += adds; }
+        msm_trace().ct_launches++;
+        MSM_TRACE(MSM_TR_GRID, L.nwg);
+        msm_fixed_ct_sim(L);
 #else
-    hipEvent_t e0{}, e1{};
-    if (stats) {
-        e0 = stats->get(); e1 = stats->get();
-        stats->ev.push_back({e0, e1});
-        HIPCHK(hipEventRecord(e0, st));
-    }
-    hipLaunchKernelGGL(k_msm_fixed_ct, dim3(L.nwg), dim3(64), 0, st, L);
-    HIPCHK(hipGetLastError());
-    if (stats) {
-        HIPCHK(hipEventRecord(e1, st));
-        stats->launches++;
-        stats->terms += terms;
-        stats->adds += adds;
-    }
+        launch_kernel(k_msm_fixed_ct, dim3(L.nwg), dim3(64), 0, st, L);
 #endif
+    });
 }
 struct MsmReq {
     MsmSeg s0, s1;
@@ -311,16 +225,12 @@ static void run_msm_multi(const bpr1cs_gens* g, MsmReq* reqs, uint32_t nreq, uin
             const uint32_t total = q.s0.count + q.s1.count;
             Small& S = sm[r];
             S.nchunks = pick_chunks(total, B, 1u << 18, q.plan->chunk);
-#if defined(BPR1CS_HOSTSIM)
-            const bool in_wave = false;      // (the simulator has no wavefronts: the functor writes one sum per chunk)
-#else
             // a wavefront per 64 chunks of ONE proof gives up what the lane-per-(chunk, proof) order has for a batch - 64 proofs reading
             // the same table rows and consecutive scalars - which only matters when a lane walks several terms: taken while a chunk is
             // one or two terms (measured: depth-32 circuit's argument, 1 proof 11.1 -> 8.8 ms, 8 proofs (2 terms per lane) 15.8 -> 16.0,
             // 64 proofs (16 terms per lane) 61 -> 135; the 64-bit bound check, one term per lane at every batch: 1 / 8 / 64 proofs
             // 6.0 / 5.9 / 7.1 -> 4.9 / 5.1 / 6.0 ms per call)
-            const bool in_wave = q.plan->chunk <= MSM_WAVE_REDUCE_MAX_CHUNK;
-#endif
+            const bool in_wave = SMALL_IN_WAVE && q.plan->chunk <= MSM_WAVE_REDUCE_MAX_CHUNK;
             S.in_wave = in_wave;
             S.groups = in_wave ? (S.nchunks + 63u) / 64u : S.nchunks;
             uint32_t cnt = S.groups;
@@ -337,35 +247,13 @@ static void run_msm_multi(const bpr1cs_gens* g, MsmReq* reqs, uint32_t nreq, uin
             S.f = K_msm_fixed_small{q.table ? q.table : g->tab.p, q.tc ? *q.tc : g->tc, {q.s0, q.s1}, S.first, B, q.plan->chunk, S.nchunks};
             if (stats) { stats->launches++; stats->terms += (uint64_t)total * B; stats->adds += (uint64_t)total * B * (q.tc ? q.tc->windows : g->tc.windows); }
         }
-#if defined(BPR1CS_HOSTSIM)
-        for (uint32_t r = 0; r < nreq; r++) launch_wave((uint64_t)sm[r].nchunks * B, sm[r].f, st);
-#else
         for (uint32_t r = 0; r < nreq;) {   // two requests of the same shape (L_k, R_k) share a launch; an empty request launches nothing
             if (sm[r].groups == 0) { r++; continue; }
             if (!sm[r].in_wave) { launch_wave((uint64_t)sm[r].nchunks * B, sm[r].f, st); r++; continue; }
             const bool pair = r + 1 < nreq && sm[r + 1].in_wave && sm[r + 1].groups == sm[r].groups;
-            const uint32_t wgs = (pair ? 2u : 1u) * sm[r].groups * B;
-            hipLaunchKernelGGL(k_msm_small_wave, dim3(wgs), dim3(64), 0, st, sm[r].f, sm[pair ? r + 1 : r].f, sm[r].groups);
-            HIPCHK(hipGetLastError());
+            launch_msm_small_pair(sm[r].f, pair ? &sm[r + 1].f : nullptr, sm[r].groups, st);
             r += pair ? 2 : 1;
         }
-#endif
-#if defined(BPR1CS_HOSTSIM)
-        for (uint32_t r = 0; r < nreq; r++) {
-            Small& S = sm[r];
-            MsmReq& q = reqs[r];
-            const ge* in = S.first;
-            uint32_t in_cnt = S.groups;
-            size_t off = S.first_off;
-            for (uint32_t t = 0; t < S.nl; t++) {
-                off -= S.lv[t];
-                ge* out = q.partial->p + off * B;
-                launch((uint64_t)S.lv[t] * B, K_ge_reduce{in, out, B, in_cnt, SMALL_REDUCE_GROUP}, st);
-                in = out; in_cnt = S.lv[t];
-            }
-            q.plan->nchunks = in_cnt;
-        }
-#else
         for (uint32_t r = 0; r < nreq;) {   // (two requests of one shape - L_k, R_k - share the launches of their levels)
             Small& S = sm[r];
             const bool pair = r + 1 < nreq && sm[r + 1].groups == S.groups && sm[r + 1].nl == S.nl && S.nl > 0;
@@ -378,15 +266,13 @@ static void run_msm_multi(const bpr1cs_gens* g, MsmReq* reqs, uint32_t nreq, uin
                     off[u] -= sm[r + u].lv[t];
                     out[u] = reqs[r + u].partial->p + off[u] * B;
                 }
-                hipLaunchKernelGGL(k_ge_reduce_wave, dim3((pair ? 2u : 1u) * S.lv[t] * B), dim3(64), 0, st, in[0], out[0], in[1], out[1], B, in_cnt, S.lv[t]);
-                HIPCHK(hipGetLastError());
+                launch_ge_reduce_pair(in, out, B, in_cnt, S.lv[t], st);
                 in[0] = out[0]; in[1] = out[1]; in_cnt = S.lv[t];
             }
             reqs[r].plan->nchunks = in_cnt;
             if (pair) reqs[r + 1].plan->nchunks = in_cnt;
             r += pair ? 2 : 1;
         }
-#endif
         return;
     }
     const uint32_t nbk = (B + 63u) / 64u;
@@ -426,7 +312,7 @@ static void run_msm_multi(const bpr1cs_gens* g, MsmReq* reqs, uint32_t nreq, uin
         L.wg_end[r] = wg;
     }
     if (ct) launch_msm_ct_kernel(L, st, stats, terms, adds);
-    else launch_msm_kernel(g, L, st, stats, terms, adds);
+    else launch_msm_kernel(L, st, stats, terms, adds);
     for (uint32_t r = 0; r < nreq; r++) {
         if (lay[r].l1) launch((uint64_t)lay[r].l1 * B, K_ge_reduce{lay[r].raw, lay[r].p1, B, lay[r].nchunks, MSM_REDUCE_GROUP}, st);
         if (lay[r].l2) launch((uint64_t)lay[r].l2 * B, K_ge_reduce{lay[r].p1, lay[r].p2, B, lay[r].l1, MSM_REDUCE_GROUP}, st);

@@ -185,16 +185,14 @@ struct JobDraws {
         const uint32_t Bd = B - Bh;
         uint64_t* raw_d = rng_raw->p + (size_t)draws * Bh * 8;
         strobe* rng_d = rng->p + Bh;
+        const dim3 wgs((Bd + 1) / 2);
         if (Bd && two_legs()) {
-            hipLaunchKernelGGL(k_rng_stream, dim3((Bd + 1) / 2), dim3(64), 0, sl, rng_d, raw_d, rng_err, Bd, d_half, rng_d);
-            HIPCHK(hipGetLastError());
+            launch_kernel(k_rng_stream, wgs, dim3(64), 0, sl, rng_d, raw_d, rng_err, Bd, d_half, rng_d);
             dev_event_create(&job->ev_rng_half);
             dev_event_record(job->ev_rng_half, sl);
-            hipLaunchKernelGGL(k_rng_stream, dim3((Bd + 1) / 2), dim3(64), 0, sl, rng_d, raw_d + (size_t)d_half * Bd * 8, rng_err, Bd, draws - d_half, (strobe*)nullptr);
-            HIPCHK(hipGetLastError());
+            launch_kernel(k_rng_stream, wgs, dim3(64), 0, sl, rng_d, raw_d + (size_t)d_half * Bd * 8, rng_err, Bd, draws - d_half, nullptr);
         } else if (Bd) {
-            hipLaunchKernelGGL(k_rng_stream, dim3((Bd + 1) / 2), dim3(64), 0, sl, rng_d, raw_d, rng_err, Bd, draws, (strobe*)nullptr);
-            HIPCHK(hipGetLastError());
+            launch_kernel(k_rng_stream, wgs, dim3(64), 0, sl, rng_d, raw_d, rng_err, Bd, draws, nullptr);
         }
         if (src == DrawsSource::Device) {
             if (shared) dev_stream_wait(sl, g->w_free_ev);

@@ -48,7 +48,8 @@
  *
  * Environment (everything the shipped library reads; none changes a result): BPR1CS_MEM_RESERVE_MB (above, read once),
  * BPR1CS_DEBUG_MEM (prints the free device memory after every large allocation), BPR1CS_DEBUG_SYNC (synchronises after every
- * launch so that a faulting kernel is named), BPR1CS_WITNESS_MACRO=0 (bpr1cs_circuit_create ignores the joint-evaluation
+ * launch - the functor kernels and the hand-written ones alike: all go through one launch function - so that a faulting kernel
+ * is named),BPR1CS_WITNESS_MACRO=0 (bpr1cs_circuit_create ignores the joint-evaluation
  * annotations of Poseidon permutations: the witness program then runs S-box by S-box - slower, same wires).  Failure
  * injection and table-geometry overrides of the test suite exist in the CPU simulator build of the tests only.
  */

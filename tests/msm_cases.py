@@ -123,8 +123,6 @@ def _plan_small(reqs, B, K, hostsim):
                          in_wave=in_wave, groups=groups, last_group=(nchunks - (groups - 1) * WAVE) if in_wave else None,
                          lv=tuple(lv), nl=len(lv), first_off=sum(lv), need=(groups + sum(lv)) * B, out_chunks=cnt,
                          launch_paired=False, reduce_paired=False))
-    if hostsim:
-        return jobs
     r = 0
     while r < len(jobs):   # the launch loop: two in-wave requests of the same shape share a launch
         if jobs[r]["groups"] == 0 or not jobs[r]["in_wave"]:

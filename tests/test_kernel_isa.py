@@ -128,20 +128,30 @@ def test_lockstep_transcript_kernels_split_the_permutation(kernels):
 
 def test_a_32_lane_workgroup_always_means_a_lockstep_transcript_launch():
     """csrc/merlin.hpp: keccak_f1600 takes the cooperative 32-lane form whenever blockDim.x == 32 (an implicit contract).
-    Made checkable: the ONLY launch with 32 threads in the library's sources is dev.hpp's launch_transcript -> k_functor_lockstep, every
-    other launch site names 64 or 256 (or a constant that is one of them), and the probe kernels take no caller-chosen block size."""
+    Made checkable: every launch goes through dev.hpp's launch_kernel (its one hipLaunchKernelGGL passes the caller's block on), directly
+    or as LAUNCH_WAVE_FORM (64 threads, stated once in the macro).  The ONLY launch_kernel site with 32 threads in the library's sources
+    is dev.hpp's launch_transcript -> k_functor_lockstep, every other site names 64 or 256 (or a constant that is one of them), and
+    the probe kernels take no caller-chosen block size."""
     csrc = os.path.join(ROOT, "bulletproofs-r1cs-gadgets_amd", "csrc")
-    sites = []
+    sites, raw = [], []
     for fn in sorted(os.listdir(csrc)):
         if not fn.endswith((".hpp", ".hip")):
             continue
         text = open(os.path.join(csrc, fn)).read()
-        for m in re.finditer(r"hipLaunchKernelGGL\(\s*((?:HIP_KERNEL_NAME\()?[\w<>:, ]+\)?)\s*,\s*dim3\(([^;]*?)\)\s*,\s*dim3\(([^)]*)\)", text, re.S):
-            sites.append((fn, m.group(1).strip(), m.group(3).strip()))
+        raw += [(fn, m.group(1)) for m in re.finditer(r"hipLaunchKernelGGL\(([^;]*);", text)]
+        for m in re.finditer(r"\blaunch_kernel\(\s*([^,;()]+?)\s*,\s*(?:dim3\([^;]*?\)|\w+)\s*,\s*dim3\(([^)]*)\)", text, re.S):
+            sites.append((fn, m.group(1).strip(), m.group(2).strip()))
+        for m in re.finditer(r"\bLAUNCH_WAVE_(?:FORM|ALWAYS)\(([^;]*?),\s*(k_\w+)\s*,", text, re.S):
+            if fn != "dev.hpp":   # (the macros' own definitions and the comment that shows their use)
+                sites.append((fn, m.group(2), "64"))
+    assert raw == [("dev.hpp", "kernel, grid, block, lds, s, static_cast<A&&>(args)...)")], raw
+    dev = open(os.path.join(csrc, "dev.hpp")).read()
+    assert re.search(r"#define LAUNCH_WAVE_FORM\(cond, grid, st, kernel, \.\.\.\) \(\(cond\) \? \(launch_kernel\(kernel, dim3\(grid\), dim3\(64\), 0, st, __VA_ARGS__\), true\) : false\)", dev)
+    assert re.search(r"#define LAUNCH_WAVE_ALWAYS\(grid, st, kernel, n, f, \.\.\.\) launch_kernel\(kernel, dim3\(grid\), dim3\(64\), 0, st, __VA_ARGS__\)", dev)
     assert len(sites) >= 20, sites
     blocks = collections.Counter(b for _, _, b in sites)
     allowed = {"64", "256", "32", "threads", "WG", "PIP_WG"}
     assert set(blocks) <= allowed, blocks
-    assert [(fn, k) for fn, k, b in sites if b == "32"] == [("dev.hpp", "HIP_KERNEL_NAME(k_functor_lockstep<F>)")]
+    assert [(fn, k) for fn, k, b in sites if b == "32"] == [("dev.hpp", "k_functor_lockstep<F>")]
     probe = open(os.path.join(csrc, "api_probe.hpp")).read()
     assert re.search(r"threads\s*=\s*256\b", probe), "api_probe.hpp: the probe kernels' block size is no longer the constant 256"

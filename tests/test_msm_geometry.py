@@ -96,6 +96,10 @@ def test_plan_gives_the_geometry_worked_out_by_hand():
     # the simulator's build: no wavefront kernels, sixteen sums per level
     assert [(x["in_wave"], x["groups"], x["lv"]) for x in _jobs("b1_t1025", hostsim=True)] == [(False, 1025, (65, 5))]
     assert [(x["groups"], x["lv"]) for x in _jobs("b2_t300", hostsim=True)] == [(300, (19, 2))] and [(x["groups"], x["nl"]) for x in _jobs("b2_t300")] == [(5, 0)]
+    # (the same two loops decide there: never a paired launch - no job is in-wave -, a paired level where two neighbours have the same levels)
+    assert [(x["groups"], x["lv"], x["launch_paired"], x["reduce_paired"]) for x in _jobs("b3_runs8", hostsim=True)] == \
+        [(20, (2,), False, True), (20, (2,), False, True), (20, (2,), False, False), (131, (9,), False, False)]
+    assert not any(x["launch_paired"] or x["reduce_paired"] for x in _jobs("b1_1025_1088", hostsim=True))   # (1025 and 1088 sums: not one shape)
     # chunks of 8 at 70 proofs: what the zero patterns are placed on
     assert M.chunk_bounds(M.case("b70_zero_term")) == [(0, 7), (8, 15), (16, 23), (24, 31), (32, 32)]
     assert [M.plan_msm(n)["chunks"] for n in M.VAR_MSM_SIZES] == [1, 1, 1, 2, 3, 64, 2, 3, 64]
