@@ -1479,6 +1479,14 @@ HD inline int vb_digit(uint32_t word, uint32_t k) {  // digit k of a packed word
     int d = (int)((word >> (VB_W * k)) & (VB_MULT * 2u - 1u));
     return d - ((d & (int)VB_MULT) << 1);
 }
+// acc + digit k of `word` times the term whose multiples 1P..16P are T[0], T[stride] ...
+HD inline ge vb_add_digit(const ge& acc, uint32_t word, uint32_t k, const ge_cached* T, size_t stride) {
+    int d = vb_digit(word, k);
+    if (d == 0) return acc;
+    int mag = d < 0 ? -d : d;
+    ge_cached e = T[(size_t)(mag - 1) * stride];
+    return ge_addsub(acc, e, d < 0);
+}
 template <int N>
 HD inline ge ge_dbln(const ge& p) {  // 2^N p: the inner doublings skip T
     ge q = p;
@@ -1569,12 +1577,7 @@ struct K_ipa_vb_win {  // one thread per (output, window, chunk, proof): sum ove
                 const uint32_t up = (q < 2) ? (out == 0) : (out != 0);
                 t = ((size_t)w * m + jj + up * h) * B + b;
             }
-            int d = vb_digit(vdig[(size_t)dw * stride + t], dk);
-            if (d != 0) {
-                int mag = d < 0 ? -d : d;
-                ge_cached e = vtab[(size_t)(mag - 1) * stride + t];
-                acc = ge_addsub(acc, e, d < 0);
-            }
+            acc = vb_add_digit(acc, vdig[(size_t)dw * stride + t], dk, vtab + t, stride);
         }
         part[g] = acc;
     }
@@ -1625,13 +1628,6 @@ struct K_ipa_vb_dig2 {  // gid = (w*m + j)*B + b over round k's layout (w: 0 G_h
         for (uint32_t i = 0; i < VB_WORDS; i++) vdig[(size_t)i * stride + g] = dig[i];
     }
 };
-HD inline ge vb_add_digit(const ge& acc, uint32_t word, uint32_t k, const ge_cached* T, size_t stride) {
-    int d = vb_digit(word, k);
-    if (d == 0) return acc;
-    int mag = d < 0 ? -d : d;
-    ge_cached e = T[(size_t)(mag - 1) * stride];
-    return ge_addsub(acc, e, d < 0);
-}
 struct K_ipa_vb_fold2 {  // gid = (side*h + j)*B + b : Ghat''[j] = Ghat[j] + w0 Ghat[j+m] + w1 Ghat[j+h] + w0 w1 Ghat[j+h+m]
     ge* GH;
     const sc* uk0;  // [2][B] u_k, u_k^-1 of the round the multiples were built in
@@ -2154,12 +2150,7 @@ struct K_msm_var_win {  // gid = win*VC + c
         const uint32_t dw = win / VB_PER_WORD, dk = win - dw * VB_PER_WORD;
         ge acc = ge_identity();
         for (uint32_t o = lo; o < hi; o++) {
-            int d = vb_digit(vdig[(size_t)dw * n + o], dk);
-            if (d != 0) {
-                int mag = d < 0 ? -d : d;
-                ge_cached e = vtab[(size_t)(mag - 1) * n + o];
-                acc = ge_addsub(acc, e, d < 0);
-            }
+            acc = vb_add_digit(acc, vdig[(size_t)dw * n + o], dk, vtab + o, n);
         }
         part[g] = acc;
     }

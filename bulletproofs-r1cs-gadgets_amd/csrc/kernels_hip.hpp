@@ -154,12 +154,16 @@ __global__ void __launch_bounds__(64) k_poseidon_team(K_poseidon_batch p, uint32
     if (active && lane < w) p.out[(size_t)h * w + lane] = sh[PS_T1 + lane];
 }
 
-// ---------------------------------------------------------------- one Pedersen commitment per wavefront
-// Prover::commit as the reference calls it - once per committed value, the result needed at once (src/gadget_vsmt_4.rs:393-410: 100
-// calls for one depth-32 proof) - is two fixed-base products of a single lane's worth of work: 2 x windows table additions one
-// after the other, then the compression.  Here every table entry is fetched by a lane of its own (digit k of a scalar is a local
-// function of its bits and the carry out of the windows below), the 2 x windows points are summed by a shuffle butterfly and lane
-// 0 compresses: ~6 dependent additions instead of 46.
+// ---------------------------------------------------------------- wavefront forms of the small-job kernels
+// A job of a few proofs leaves most of the chip idle while single lanes walk long chains of dependent additions.  The kernels of
+// this section put one output (a commitment, a T, L_k / R_k, a verifier's or a range's finish, a sum of scalars) on the 64 lanes of
+// a wavefront: every lane takes the items idx = lane, lane + 64 ... of the output, and a shuffle butterfly adds the 64 shares.
+// The shared steps, each stated once:
+//   wave_sum(sc) / wave_sum(ge) / wave_or   the butterflies: every lane ends with the result over all 64 lanes;
+//   WaveAcc                                 a lane's share of a sum of points: table items (table_entry: the step of
+//                                           table_mul_acc_raw, kernels.hpp), plain points (point) and the butterfly (total);
+//   commit_wave                             a Pedersen commitment s0 * B0 + s1 * B1 from one table, compressed.
+// Sums in the group and mod l do not depend on the order, so the bytes are those of the lane functors of kernels.hpp.
 __device__ inline ge ge_shfl_xor(const ge& p, int mask) {
     ge o;
 #pragma unroll
@@ -171,25 +175,79 @@ __device__ inline ge ge_shfl_xor(const ge& p, int mask) {
     }
     return o;
 }
-__global__ void __launch_bounds__(64) k_commit_wave(const uint8_t* tab, TabCfg tc, const sc* v_raw, const sc* vbl_raw, uint8_t* out, uint32_t B, uint32_t m) {
-    const uint32_t g = blockIdx.x, lane = threadIdx.x;   // g = j*B + b
-    const uint32_t j = g / B, b = g % B;
-    ge acc = ge_identity();
-    for (uint32_t idx = lane; idx < 2u * tc.windows; idx += 64u) {
-        const uint32_t t = idx / tc.windows, k = idx % tc.windows;
-        const sc s = t ? vbl_raw[g] : v_raw[g];
+__device__ inline sc sc_shfl_xor(const sc& s, int mask) {
+    sc o;
+#pragma unroll
+    for (int i = 0; i < 8; i++) o.v[i] = (uint32_t)__shfl_xor((int)s.v[i], mask, 64);
+    return o;
+}
+// every lane ends with the sum of all 64 (team_sum<T> above is the witness kernel's form of the scalar one: unrolled, width T)
+__device__ inline sc wave_sum(sc acc) {
+#pragma unroll 1
+    for (int sft = 32; sft > 0; sft >>= 1) acc = sc_add(acc, sc_shfl_xor(acc, sft));
+    return acc;
+}
+__device__ inline ge wave_sum(ge acc) {
+#pragma unroll 1
+    for (int sft = 32; sft > 0; sft >>= 1) acc = ge_add_ge(acc, ge_shfl_xor(acc, sft));   // (a ge_add_ge is large: one copy, not six)
+    return acc;
+}
+__device__ inline int wave_or(int flag) { return __any(flag); }   // nonzero on every lane if any lane's flag is
+
+// A lane's share of one output.  Its items come in the order table items first, then chunk sums, then own points (per lane too:
+// every enumeration puts the table items first), so the accumulator enters the table class (ge_madd_t) at most once and leaves
+// it (ge_from_table_class) at most once: before the first plain point, or in total().  A lane that added no table entry never
+// entered it and skips the hand-over - the group element is the same either way, so are the compressed bytes.
+struct WaveAcc {
+    ge acc;
+    bool table_class;
+    // digit k of s, times the base of tbase: table_mul_acc_raw's step (kernels.hpp) with its loop over k handed out to the lanes.
+    // The carry into window k is a scan of the windows below (integer ops only).
+    __device__ void table_entry(const uint8_t* tbase, const TabCfg& tc, const sc& s, uint32_t k) {
         int carry = 0, d = 0;
-        for (uint32_t kk = 0; kk <= k; kk++) d = tab_digit(s, kk, carry, tc);   // the carry into window k: a scan of the windows below (integer ops only)
+        for (uint32_t kk = 0; kk <= k; kk++) d = tab_digit(s, kk, carry, tc);
         if (d != 0) {
             const int neg = d < 0;
             const uint32_t mag = (uint32_t)(neg ? -d : d);
-            acc = ge_madd_t(acc, ge_niels_load(tab + (size_t)t * tc.base_bytes() + ((size_t)k * tc.row + mag) * tc.stride), neg);
+            acc = ge_madd_t(acc, ge_niels_load(tbase + ((size_t)k * tc.row + mag) * tc.stride), neg);
+            table_class = true;
         }
     }
-    acc = ge_from_table_class(acc);
-#pragma unroll 1
-    for (int sft = 32; sft > 0; sft >>= 1) acc = ge_add_ge(acc, ge_shfl_xor(acc, sft));   // every lane ends with the sum of all 64
-    ge_compress_wave(acc, out + ((size_t)b * m + j) * 32);
+    // item idx < 2 x windows of s0 * B0 + s1 * B1, the two bases of one table
+    __device__ void table2_entry(const uint8_t* tab, const TabCfg& tc, const sc& s0, const sc& s1, uint32_t idx) {
+        const uint32_t t = idx / tc.windows, k = idx % tc.windows;
+        const sc s = t ? s1 : s0;   // (a copy of its own: the digit scan indexes its words)
+        table_entry(tab + (size_t)t * tc.base_bytes(), tc, s, k);
+    }
+    __device__ void leave_table_class() {
+        if (table_class) { acc = ge_from_table_class(acc); table_class = false; }
+    }
+    __device__ void point(const ge& p) {
+        leave_table_class();
+        acc = ge_add_ge(acc, p);
+    }
+    __device__ ge total() {   // on every lane: the sum over the 64 lanes' shares
+        leave_table_class();
+        return wave_sum(acc);
+    }
+};
+
+// ---------------------------------------------------------------- one Pedersen commitment per wavefront
+// Prover::commit as the reference calls it - once per committed value, the result needed at once (src/gadget_vsmt_4.rs:393-410: 100
+// calls for one depth-32 proof) - is two fixed-base products of a single lane's worth of work: 2 x windows table additions one
+// after the other, then the compression.  Here every table entry is fetched by a lane of its own (digit k of a scalar is a local
+// function of its bits and the carry out of the windows below), the 2 x windows points are summed by a shuffle butterfly and lane
+// 0 compresses: ~6 dependent additions instead of 46.  (Lanes past 2 x windows add nothing and stay out of the table class: 18 of
+// 64 at the default 23 windows - the intended form, see WaveAcc.)
+__device__ inline void commit_wave(const uint8_t* tab, const TabCfg& tc, const sc& s0, const sc& s1, uint8_t* out) {
+    WaveAcc w{ge_identity(), false};
+    for (uint32_t idx = threadIdx.x; idx < 2u * tc.windows; idx += 64u) w.table2_entry(tab, tc, s0, s1, idx);
+    ge_compress_wave(w.total(), out);
+}
+__global__ void __launch_bounds__(64) k_commit_wave(const uint8_t* tab, TabCfg tc, const sc* v_raw, const sc* vbl_raw, uint8_t* out, uint32_t B, uint32_t m) {
+    const uint32_t g = blockIdx.x;   // g = j*B + b
+    const uint32_t j = g / B, b = g % B;
+    commit_wave(tab, tc, v_raw[g], vbl_raw[g], out + ((size_t)b * m + j) * 32);
 }
 
 // K_sum_partials for a job of a few proofs: a wavefront per output.  One thread adding up to 256 chunk sums one after the other is
@@ -200,13 +258,7 @@ __global__ void __launch_bounds__(64) k_sum_partials_wave(K_sum_partials f) {
     const uint32_t k = g / f.B, b = g % f.B;
     sc acc = sc_zero();
     for (uint32_t c = lane; c < f.C; c += 64u) acc = sc_add(acc, f.part[((size_t)k * f.C + c) * f.B + b]);
-#pragma unroll 1
-    for (int sft = 32; sft > 0; sft >>= 1) {
-        sc o;
-#pragma unroll
-        for (int i = 0; i < 8; i++) o.v[i] = (uint32_t)__shfl_xor((int)acc.v[i], sft, 64);
-        acc = sc_add(acc, o);
-    }
+    acc = wave_sum(acc);
     if (lane == 0) f.out[g] = acc;
 }
 
@@ -216,33 +268,21 @@ __global__ void __launch_bounds__(64) k_dot_wave(const sc* x, const sc* y, sc* o
     const uint32_t b = blockIdx.x, lane = threadIdx.x;
     sc acc = sc_zero();
     for (uint32_t j = lane; j < m; j += 64u) acc = sc_add(acc, sc_mul(x[(size_t)j * B + b], y[(size_t)j * B + b]));
-#pragma unroll 1
-    for (int sft = 32; sft > 0; sft >>= 1) {
-        sc o;
-#pragma unroll
-        for (int i = 0; i < 8; i++) o.v[i] = (uint32_t)__shfl_xor((int)acc.v[i], sft, 64);
-        acc = sc_add(acc, o);
-    }
+    acc = wave_sum(acc);
     if (lane == 0) out[b] = acc;
 }
 
 // K_verify_public for a batch of a few proofs: a wavefront per proof, the lanes take every 64th public input (the canonical test,
-// the conversion and the product of a term are public_term's, as in the functor) and a shuffle butterfly adds the 64 partial sums
-// and ORs their flags - as k_dot_wave; the sum mod l does not depend on the order.
+// the conversion and the product of a term are public_term's, as in the functor), a shuffle butterfly adds the 64 partial sums
+// - as k_dot_wave; the sum mod l does not depend on the order - and the lanes' flags are ORed.
 __global__ void __launch_bounds__(64) k_verify_public_wave(K_verify_public f) {
     const uint32_t b = blockIdx.x, lane = threadIdx.x;
     if (b >= f.B) return;   // (whole wavefront: blockIdx is uniform)
     sc acc = sc_zero();
     int bad = 0;
     for (uint32_t k = lane; k < f.p; k += 64u) acc = sc_add(acc, public_term(f.wpub, f.pub, f.B, f.p, b, k, bad));
-#pragma unroll 1
-    for (int sft = 32; sft > 0; sft >>= 1) {
-        sc o;
-#pragma unroll
-        for (int i = 0; i < 8; i++) o.v[i] = (uint32_t)__shfl_xor((int)acc.v[i], sft, 64);
-        acc = sc_add(acc, o);
-        bad |= __shfl_xor(bad, sft, 64);
-    }
+    acc = wave_sum(acc);
+    bad = wave_or(bad);
     if (lane == 0) {
         if (bad) f.fail[b] = 1;
         else f.wc[b] = sc_add(f.wc[b], acc);
@@ -252,27 +292,11 @@ __global__ void __launch_bounds__(64) k_verify_public_wave(K_verify_public f) {
 // K_commit_T for a job of a few proofs: a wavefront per T commitment (as k_commit_wave: table entries on 2 x windows lanes, butterfly,
 // lane 0 compresses) instead of a lane walking 2 x windows additions.
 __global__ void __launch_bounds__(64) k_commit_T_wave(K_commit_T f) {
-    const uint32_t g = blockIdx.x, lane = threadIdx.x;
+    const uint32_t g = blockIdx.x;
     const uint32_t k = g / f.B, b = g % f.B;
     const uint32_t ti[5] = {0, 2, 3, 4, 5};
-    const TabCfg tc = f.tc;
     const sc s0 = sc_from_mont(f.tco[(size_t)ti[k] * f.B + b]), s1 = sc_from_mont(f.blind[(size_t)(3 + k) * f.B + b]);
-    ge acc = ge_identity();
-    for (uint32_t idx = lane; idx < 2u * tc.windows; idx += 64u) {
-        const uint32_t t = idx / tc.windows, w = idx % tc.windows;
-        const sc s = t ? s1 : s0;
-        int carry = 0, d = 0;
-        for (uint32_t kk = 0; kk <= w; kk++) d = tab_digit(s, kk, carry, tc);
-        if (d != 0) {
-            const int neg = d < 0;
-            const uint32_t mag = (uint32_t)(neg ? -d : d);
-            acc = ge_madd_t(acc, ge_niels_load(f.tab + (size_t)t * tc.base_bytes() + ((size_t)w * tc.row + mag) * tc.stride), neg);
-        }
-    }
-    acc = ge_from_table_class(acc);
-#pragma unroll 1
-    for (int sft = 32; sft > 0; sft >>= 1) acc = ge_add_ge(acc, ge_shfl_xor(acc, sft));
-    ge_compress_wave(acc, f.out + 32 * (size_t)g);
+    commit_wave(f.tab, f.tc, s0, s1, f.out + 32 * (size_t)g);
 }
 
 // K_pow_tables for a job of a few proofs: a wavefront per (y | y^-1 | z, proof).  The functor's thread multiplies its way through
@@ -321,32 +345,20 @@ __device__ inline ge msm_finish_wave(const K_msm_finish& f, uint32_t b, uint32_t
         e1 = f.extra2 ? sc_from_mont(sc_mul(e1, f.extra2[b])) : sc_from_mont(e1);
     }
     if (n_t2) e2 = sc_from_mont(f.extra_b[b]);
-    ge acc = (lane == 0 && f.shared_pt) ? f.shared_pt[0] : ge_identity();
-    bool table_class = false;
-    for (uint32_t idx = lane; idx < n_items; idx += 64u) {   // (per lane: table items first - the enumeration puts them first)
+    WaveAcc w{(lane == 0 && f.shared_pt) ? f.shared_pt[0] : ge_identity(), false};
+    for (uint32_t idx = lane; idx < n_items; idx += 64u) {
         if (idx < n_tab) {
             const bool second = idx >= n_t1;
             const uint32_t k = second ? idx - n_t1 : idx;
             const sc s = second ? e2 : e1;
             const uint8_t* tb = second ? f.tab2 : f.tab + (size_t)f.extra_base * tc.base_bytes();
-            int carry = 0, d = 0;
-            for (uint32_t kk = 0; kk <= k; kk++) d = tab_digit(s, kk, carry, tc);
-            if (d != 0) {
-                const int neg = d < 0;
-                const uint32_t mag = (uint32_t)(neg ? -d : d);
-                acc = ge_madd_t(acc, ge_niels_load(tb + ((size_t)k * tc.row + mag) * tc.stride), neg);
-                table_class = true;
-            }
+            w.table_entry(tb, tc, s, k);
         } else {
-            if (table_class) { acc = ge_from_table_class(acc); table_class = false; }
             const uint32_t c = idx - n_tab;
-            acc = ge_add_ge(acc, c < f.nchunks ? f.partial[(size_t)c * f.B + b] : f.partial_b[(size_t)(c - f.nchunks) * f.B + b]);
+            w.point(c < f.nchunks ? f.partial[(size_t)c * f.B + b] : f.partial_b[(size_t)(c - f.nchunks) * f.B + b]);
         }
     }
-    if (table_class) acc = ge_from_table_class(acc);
-#pragma unroll 1
-    for (int sft = 32; sft > 0; sft >>= 1) acc = ge_add_ge(acc, ge_shfl_xor(acc, sft));
-    return acc;
+    return w.total();
 }
 __global__ void __launch_bounds__(64) k_finish_wave(K_msm_finish fa, K_msm_finish fb, K_msm_finish fc, uint32_t B) {
     const uint32_t g = blockIdx.x, inst = g / B, b = g % B;
@@ -365,14 +377,9 @@ __global__ void __launch_bounds__(64) k_verify_win_wave(const ge_cached* vtab, c
     ge acc = ge_identity();
     for (uint32_t p = lane; p < P; p += 64u) {
         const size_t t = (size_t)p * B + b;
-        const int d = vb_digit(vdig[(size_t)dw * T + t], dk);
-        if (d != 0) {
-            const int mag = d < 0 ? -d : d;
-            acc = ge_addsub(acc, vtab[(size_t)(mag - 1) * T + t], d < 0);
-        }
+        acc = vb_add_digit(acc, vdig[(size_t)dw * T + t], dk, vtab + t, T);
     }
-#pragma unroll 1
-    for (int sft = 32; sft > 0; sft >>= 1) acc = ge_add_ge(acc, ge_shfl_xor(acc, sft));
+    acc = wave_sum(acc);
     if (lane == 0) part[(size_t)win * B + b] = acc;
 }
 
@@ -384,29 +391,15 @@ __global__ void __launch_bounds__(64) k_verify_finish_wave(K_verify_finish f) {
     const TabCfg tc = f.tc;
     const uint32_t n_tab = 2u * tc.windows, n_items = n_tab + f.nchunks + f.P;
     const sc e1 = sc_from_mont(f.bsc[b]), e2 = sc_from_mont(f.bsc[(size_t)f.B + b]);
-    ge acc = ge_identity();
-    bool table_class = false;
-    for (uint32_t idx = lane; idx < n_items; idx += 64u) {   // (per lane: table items first - the enumeration puts them first)
-        if (idx < n_tab) {
-            const uint32_t t = idx / tc.windows, k = idx % tc.windows;
-            const sc s = t ? e2 : e1;
-            int carry = 0, d = 0;
-            for (uint32_t kk = 0; kk <= k; kk++) d = tab_digit(s, kk, carry, tc);
-            if (d != 0) {
-                const int neg = d < 0;
-                const uint32_t mag = (uint32_t)(neg ? -d : d);
-                acc = ge_madd_t(acc, ge_niels_load(f.tab + (size_t)t * tc.base_bytes() + ((size_t)k * tc.row + mag) * tc.stride), neg);
-                table_class = true;
-            }
-        } else {
-            if (table_class) { acc = ge_from_table_class(acc); table_class = false; }
+    WaveAcc w{ge_identity(), false};
+    for (uint32_t idx = lane; idx < n_items; idx += 64u) {
+        if (idx < n_tab) w.table2_entry(f.tab, tc, e1, e2, idx);
+        else {
             const uint32_t c = idx - n_tab;
-            acc = ge_add_ge(acc, c < f.nchunks ? f.msm_partial[(size_t)c * f.B + b] : f.pts[(size_t)(c - f.nchunks) * f.B + b]);
+            w.point(c < f.nchunks ? f.msm_partial[(size_t)c * f.B + b] : f.pts[(size_t)(c - f.nchunks) * f.B + b]);
         }
     }
-    if (table_class) acc = ge_from_table_class(acc);
-#pragma unroll 1
-    for (int sft = 32; sft > 0; sft >>= 1) acc = ge_add_ge(acc, ge_shfl_xor(acc, sft));
+    const ge acc = w.total();
     uint8_t enc[32];
     ge_compress_t(acc, enc, fe_pow_wave{});
     if (lane == 0) f.ok[b] = (!f.fail[b]) && bytes_are_zero32(enc);
@@ -430,13 +423,7 @@ __global__ void __launch_bounds__(64) k_combine_scalars_range_wave(K_combine_sca
         sc acc = sc_zero();
         for (uint32_t b = lo + lane; b < hi; b += 64u)
             if (!f.fail[b]) acc = sc_add(acc, sc_mul(in_row[b], f.rho[b]));
-#pragma unroll 1
-        for (int sft = 32; sft > 0; sft >>= 1) {
-            sc o;
-#pragma unroll
-            for (int i = 0; i < 8; i++) o.v[i] = (uint32_t)__shfl_xor((int)acc.v[i], sft, 64);
-            acc = sc_add(acc, o);
-        }
+        acc = wave_sum(acc);
         if (lane == 0) f.out[g] = acc;
     }
 }
@@ -450,8 +437,7 @@ __global__ void __launch_bounds__(64) k_range_points_wave(K_range_points f) {
         const uint32_t p = idx / cnt, j = idx - p * cnt;
         if (!f.fail[lo + j]) acc = ge_add_ge(acc, f.pts[(size_t)p * f.B + lo + j]);
     }
-#pragma unroll 1
-    for (int sft = 32; sft > 0; sft >>= 1) acc = ge_add_ge(acc, ge_shfl_xor(acc, sft));
+    acc = wave_sum(acc);
     if (lane == 0) f.out[r] = acc;
 }
 // K_range_finish with a wavefront per range (a depth's handful of ranges): table entries, chunk sums and the range's own-point sum are
@@ -462,29 +448,15 @@ __global__ void __launch_bounds__(64) k_range_finish_wave(K_range_finish f) {
     const TabCfg tc = f.tc;
     const uint32_t n_tab = 2u * tc.windows, n_items = n_tab + f.nchunks + 1u;
     const sc e1 = sc_from_mont(f.bsc[r]), e2 = sc_from_mont(f.bsc[(size_t)f.R + r]);
-    ge acc = ge_identity();
-    bool table_class = false;
-    for (uint32_t idx = lane; idx < n_items; idx += 64u) {   // (per lane: table items first - the enumeration puts them first)
-        if (idx < n_tab) {
-            const uint32_t t = idx / tc.windows, k = idx % tc.windows;
-            const sc s = t ? e2 : e1;
-            int carry = 0, d = 0;
-            for (uint32_t kk = 0; kk <= k; kk++) d = tab_digit(s, kk, carry, tc);
-            if (d != 0) {
-                const int neg = d < 0;
-                const uint32_t mag = (uint32_t)(neg ? -d : d);
-                acc = ge_madd_t(acc, ge_niels_load(f.tab + (size_t)t * tc.base_bytes() + ((size_t)k * tc.row + mag) * tc.stride), neg);
-                table_class = true;
-            }
-        } else {
-            if (table_class) { acc = ge_from_table_class(acc); table_class = false; }
+    WaveAcc w{ge_identity(), false};
+    for (uint32_t idx = lane; idx < n_items; idx += 64u) {
+        if (idx < n_tab) w.table2_entry(f.tab, tc, e1, e2, idx);
+        else {
             const uint32_t c = idx - n_tab;
-            acc = ge_add_ge(acc, c < f.nchunks ? f.msm_partial[(size_t)c * f.R + r] : f.rpts[r]);
+            w.point(c < f.nchunks ? f.msm_partial[(size_t)c * f.R + r] : f.rpts[r]);
         }
     }
-    if (table_class) acc = ge_from_table_class(acc);
-#pragma unroll 1
-    for (int sft = 32; sft > 0; sft >>= 1) acc = ge_add_ge(acc, ge_shfl_xor(acc, sft));
+    const ge acc = w.total();
     if (lane == 0) f.left[r] = acc;
     uint8_t enc[32];
     int right_zero = 0;
@@ -511,8 +483,7 @@ __global__ void __launch_bounds__(64) k_msm_small_wave(K_msm_fixed_small fa, K_m
     const K_msm_fixed_small& f = r ? fb : fa;
     const uint32_t c = w * 64u + threadIdx.x;
     ge acc = c < f.nchunks ? f.chunk_sum(c, b) : ge_identity();
-#pragma unroll 1
-    for (int sft = 32; sft > 0; sft >>= 1) acc = ge_add_ge(acc, ge_shfl_xor(acc, sft));
+    acc = wave_sum(acc);
     if (threadIdx.x == 0) f.partial[(size_t)w * f.B + b] = acc;
 }
 
@@ -526,8 +497,7 @@ __global__ void __launch_bounds__(64) k_ge_reduce_wave(const ge* in_a, ge* out_a
     ge* out = r ? out_b : out_a;
     const uint32_t c = w * 64u + threadIdx.x;
     ge acc = c < in_cnt ? in[(size_t)c * B + b] : ge_identity();
-#pragma unroll 1
-    for (int sft = 32; sft > 0; sft >>= 1) acc = ge_add_ge(acc, ge_shfl_xor(acc, sft));
+    acc = wave_sum(acc);
     if (threadIdx.x == 0) out[(size_t)w * B + b] = acc;
 }
 

@@ -23,6 +23,26 @@ def test_compiled_poseidon(hip_lib, hip_glib, case):
     fc.check_compiled(hip_lib, hip_glib, case, batch=2, unfold=4)
 
 
+@pytest.mark.parametrize("case,batch,unfold", [("bound_check", 3, 2), ("poseidon_hash_2_inverse", 2, 4)])
+def test_compiled_with_four_bit_windows(hip_lib, hip_glib, case, batch, unfold):
+    """W = 4: 64 windows per base, so a wavefront kernel's two fixed-base products are 128 table items and every lane makes a second
+    trip - k_commit_T_wave (two table items per lane) and k_finish_wave (table items, then chunk sums, on one lane; the Poseidon
+    circuit adds the second chunk list of A_I, the shared ones point of A_O and, in the last job, the second table term of L_0).
+    The other tests of this file run at W = 8: 64 table items, one per lane.  Same cases and batches as above (the oracle's proofs
+    are shared).  Three jobs on one circuit and one handle: the small job, then its witnesses 33 times over - more than 64 proofs:
+    the lane functors, and the job that builds the table of round 0's summed padding generators -, then the small job again, which
+    finds that table and takes L_0's block through it."""
+    bp = fc.bp
+    gname, ip, sp, _, cap = fc.case(case, 0)
+    ob = fc.common.oracle_batch(lambda j: fc.case(case, j)[3], cap, batch, key=case)
+    circ = bp.CompiledGadget(gname, ip, sp, lib=hip_lib, glib=hip_glib)
+    gens = bp.Gens(cap, lib=hip_lib, window_bits=4, unfold=unfold)
+    assert gens.table_info()["windows"] == 64
+    for reps in (1, 33, 1):
+        P, _ = bp.prove_batch(gens, circ, ob["label"], ob["values"] * reps, ob["blindings"] * reps, ob["seeds"] * reps, batch * reps, wires=None)
+        assert P == ob["proofs"] * reps, "reps = %d" % reps
+
+
 def test_compiled_vsmt_2(hip_lib, hip_glib):
     fc.check_compiled(hip_lib, hip_glib, "vsmt_2_d3", batch=2, unfold=4)
 
