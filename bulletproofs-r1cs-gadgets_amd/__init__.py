@@ -19,6 +19,7 @@ POSEIDON_PARAMS_PATH = os.path.join(_HERE, "data", "poseidon_params_ristretto.bi
 VAR_COMMITTED, VAR_MUL_LEFT, VAR_MUL_RIGHT, VAR_MUL_OUT, VAR_ONE = 0, 1, 2, 3, 4
 VAR_PUBLIC = 5   # public input k of the proof at hand (include/bpr1cs.h "Public inputs"): its value rides in the calls' `publics`
 W_LC, W_INV_LEFT, W_BIT, W_NOTBIT = 0, 1, 2, 3
+W_AUX = 10  # auxiliary input #arg of the proof at hand (include/bpr1cs.h "Auxiliary inputs"): its value rides in the prove calls' `aux`
 W_LCBIT, W_LCNOTBIT = 4, 5    # bit (arg & 0xff) of the canonical value of linear combination #(arg >> 8); 1 - that bit
 
 ERRORS = {0: "OK", -1: "InvalidGeneratorsLength", -2: "FormatError", -3: "VerificationError",
@@ -157,15 +158,31 @@ def _u32arr(xs):
     return (ctypes.c_uint32 * max(1, len(xs)))(*xs)
 
 
-def _tail(block, publics, circuit, batch):
+def _rows(block):
+    if not isinstance(block, (bytes, bytearray)):
+        block = b"".join(_sc(x) for row in block for x in (row if isinstance(row, (list, tuple)) else [row]))
+    return bytes(block)
+
+
+_NO_AUX = object()   # (a verify call: the auxiliary block is the prover's alone)
+
+
+def _tail(block, publics, circuit, batch, aux=_NO_AUX, wires=None):
     """`values` / `commitments` of a call with the public inputs behind them (include/bpr1cs.h: the tail block, batch x p x 32 bytes,
-    proof-major); a circuit without public inputs takes none"""
+    proof-major); a circuit without public inputs takes none.  A prove call passes `aux` (and its `wires`): the auxiliary inputs,
+    batch x a x 32 bytes, go behind the public ones; with host wires the library does not read them and `aux` may be None"""
     p = getattr(circuit, "p", 0)
-    publics = publics or b""
-    if not isinstance(publics, (bytes, bytearray)):
-        publics = b"".join(_sc(x) for row in publics for x in (row if isinstance(row, (list, tuple)) else [row]))
+    publics = _rows(publics or b"")
     assert len(publics) == batch * p * 32, "publics: %d bytes, the circuit takes %d x %d x 32" % (len(publics), batch, p)
-    return bytes(block) + bytes(publics) if p else block
+    out = bytes(block) + publics if p else block
+    if aux is _NO_AUX:
+        return out
+    a = getattr(circuit, "a", 0)
+    if aux is None and (wires is not None or a == 0):
+        return out
+    aux = _rows(aux or b"")
+    assert len(aux) == batch * a * 32, "aux: %d bytes, the circuit takes %d x %d x 32" % (len(aux), batch, a)
+    return bytes(out) + aux if a else out
 
 
 class Gens:
@@ -227,6 +244,7 @@ class Circuit:
     constraints: list of rows, each a list of ((kind, index), coeff_int_or_bytes); kind VAR_PUBLIC = public input `index`
     wops: optional list of (lkind, larg, rkind, rarg); lcs: list of term lists for W_LC / W_LCBIT / W_LCNOTBIT operands.
     .p: public inputs per proof (1 + the highest index used, as the library derives it; raw=: scanned from the variable list).
+    .a: auxiliary inputs per proof (1 + the highest index a W_AUX operand of `wops` names, as the library derives it; 0 without wops).
     """
 
     def __init__(self, n, m, constraints, wops=None, lcs=None, lib=None, raw=None):
@@ -246,6 +264,8 @@ class Circuit:
         pub = [v & 0x0fffffff for v in tvar if v >> 28 == VAR_PUBLIC]
         pub += [idx for terms in (lcs or []) if wops is not None for (kind, idx), _ in terms if kind == VAR_PUBLIC]
         self.p = 1 + max(pub) if pub else 0
+        aux = [arg for w in (wops or []) for kind, arg in ((w[0], w[1]), (w[2], w[3])) if kind == W_AUX]
+        self.a = 1 + max(aux) if aux else 0
         d = _CircuitDesc()
         d.n, d.q, d.m = n, q, m
         self._keep = [_u32arr(row_off), _u32arr(tvar), bytes(tcoef) or b"\0"]
@@ -278,9 +298,11 @@ class Circuit:
             pass
 
 
-def prove_batch(gens, circuit, label, values, v_blindings, rng_seeds, batch, wires=None, publics=None):
+def prove_batch(gens, circuit, label, values, v_blindings, rng_seeds, batch, wires=None, publics=None, aux=None):
     """-> (list of proof bytes, list of per-proof commitment lists).
     publics: the public inputs of a circuit that has any - bytes batch*p*32 proof-major, or a list of per-proof lists.
+    aux: the auxiliary inputs (W_AUX operands) of a circuit that has any - bytes batch*a*32 proof-major, or a list of per-proof
+    lists; read by the device witness program only: may be None when `wires` is given.
 
     values / v_blindings: bytes batch*m*32 proof-major; rng_seeds: bytes batch*32;
     wires: None (device witness program) or bytes batch*3*n*32 (a_L|a_R|a_O per proof).
@@ -292,7 +314,7 @@ def prove_batch(gens, circuit, label, values, v_blindings, rng_seeds, batch, wir
         assert len(wires) == batch * 3 * circuit.n * 32
     proofs = ctypes.create_string_buffer(batch * plen)
     comms = ctypes.create_string_buffer(max(1, batch * m * 32))
-    values = _tail(values, publics, circuit, batch)
+    values = _tail(values, publics, circuit, batch, aux, wires)
     _chk(lib.bpr1cs_prove_batch(gens.h, circuit.h, label, len(label), values or b"\0", v_blindings or b"\0", rng_seeds,
                                 wires, batch, proofs, comms))
     praw, craw = proofs.raw, comms.raw  # .raw copies the whole buffer: take it once
@@ -539,9 +561,9 @@ def points_sum_is_identity(points, lib=None):
 class ProveJob:
     """An in-flight bpr1cs_prove_batch_begin; .finish() -> (proofs, commitments)."""
 
-    def __init__(self, gens, circuit, label, values, v_blindings, rng_seeds, batch, wires=None, publics=None):
+    def __init__(self, gens, circuit, label, values, v_blindings, rng_seeds, batch, wires=None, publics=None, aux=None):
         self.lib, self.batch, self.m, self.plen = gens.lib, batch, circuit.m, circuit.proof_len
-        values = _tail(values, publics, circuit, batch)
+        values = _tail(values, publics, circuit, batch, aux, wires)
         h = ctypes.c_void_p()
         _chk(self.lib.bpr1cs_prove_batch_begin(gens.h, circuit.h, label, len(label), values or b"\0", v_blindings or b"\0", rng_seeds,
                                                wires, batch, ctypes.byref(h)))
@@ -570,7 +592,7 @@ def last_prove_stats(lib=None):
                 refused=st.refused)
 
 
-def prove_batch_transcripts(gens, circuit, transcripts, values, v_blindings, rng_seeds, batch, wires=None, publics=None):
+def prove_batch_transcripts(gens, circuit, transcripts, values, v_blindings, rng_seeds, batch, wires=None, publics=None, aux=None):
     """bpr1cs_prove_batch_transcripts: `transcripts` = one Transcript (every proof starts from a copy) or `batch` of them (each is
     advanced to the state upstream's `&mut transcript` has after prove()) -> (proofs, commitments) as prove_batch"""
     lib = gens.lib
@@ -579,7 +601,7 @@ def prove_batch_transcripts(gens, circuit, transcripts, values, v_blindings, rng
     m, plen = circuit.m, circuit.proof_len
     proofs = ctypes.create_string_buffer(batch * plen)
     comms = ctypes.create_string_buffer(max(1, batch * m * 32))
-    values = _tail(values, publics, circuit, batch)
+    values = _tail(values, publics, circuit, batch, aux, wires)
     _chk(lib.bpr1cs_prove_batch_transcripts(gens.h, circuit.h, arr, len(ts), values or b"\0", v_blindings or b"\0", rng_seeds, wires, batch, proofs, comms))
     praw, craw = proofs.raw, comms.raw
     return ([praw[i * plen:(i + 1) * plen] for i in range(batch)],
@@ -595,11 +617,11 @@ def output_buffers(circuit, batch):
     return bufs
 
 
-def prove_batch_raw(gens, circuit, label, values, v_blindings, rng_seeds, batch, out=None, publics=None):
+def prove_batch_raw(gens, circuit, label, values, v_blindings, rng_seeds, batch, out=None, publics=None, aux=None):
     """ONE bpr1cs_prove_batch call over any batch (the library cuts it into device jobs) -> (proof bytes, commitment bytes), unsplit.
     out: (proofs, commitments) from output_buffers() - filled in place and returned as they are (no copy)"""
     m, plen = circuit.m, circuit.proof_len
-    values = _tail(values, publics, circuit, batch)
+    values = _tail(values, publics, circuit, batch, aux)
     if out is not None:
         pbuf, cbuf = out
         assert len(pbuf) >= batch * plen and len(cbuf) >= max(1, batch * m * 32)
@@ -663,11 +685,18 @@ def _sc(x):
     return x if isinstance(x, (bytes, bytearray)) else int(x).to_bytes(32, "little")
 
 
+def gadget_aux_count(name, iparams):
+    """auxiliary inputs per proof of a gadget name (host/frontend.cpp run_gadget): the proof nodes of the lean tree forms"""
+    return {"vsmt_4_aux": 3, "vsmt_2_aux": 1}.get(name, 0) * (iparams[0] if iparams else 0)
+
+
 class CompiledGadget:
     """A reference gadget compiled (shape only) into a device circuit + witness program.
     The tree gadgets ("vsmt_4", "vsmt_2") compiled WITHOUT sparams take the root as public input 0 of every proof (.p == 1): one
     circuit then proves and verifies memberships in different trees, `publics` = the roots.  "bound_check_1" (iparams = [bits], ONE
-    committed value) compiled without sparams takes its bounds as public inputs 0 and 1 (.p == 2), `publics` = (min, max) per proof."""
+    committed value) compiled without sparams takes its bounds as public inputs 0 and 1 (.p == 2), `publics` = (min, max) per proof.
+    "vsmt_4_aux" / "vsmt_2_aux": the tree gadgets with the proof nodes as auxiliary inputs (.a = 3 * levels / depth; .m = 4 / 5 + depth):
+    the prove calls take the nodes as `aux`, the verifiers never see them."""
 
     def __init__(self, name, iparams=(), sparams=(), lib=None, glib=None):
         self.lib = lib or load_library()
@@ -681,7 +710,8 @@ class CompiledGadget:
         self.h, self.n, self.q, self.m, self.has_witness_program = h, n.value, q.value, m.value, bool(hw.value)
         self.proof_len = self.lib.bpr1cs_proof_len(h)
         # (host/frontend.cpp run_gadget: the root as Variable::Public(0); the bounds of bound_check_1 as Public(0), Public(1))
-        self.p = {"vsmt_4": 1, "vsmt_2": 1, "bound_check_1": 2}.get(name, 0) if len(sparams) == 0 else 0
+        self.p = {"vsmt_4": 1, "vsmt_2": 1, "vsmt_4_aux": 1, "vsmt_2_aux": 1, "bound_check_1": 2}.get(name, 0) if len(sparams) == 0 else 0
+        self.a = gadget_aux_count(name, list(iparams))
 
     def close(self):
         if self.h:
@@ -707,7 +737,7 @@ def prove_single(name, iparams, sparams, gens_capacity, label, values, blindings
     _chk(g.bpr1cs_gadget_prove_single(name.encode(), _u32arr(list(iparams)), len(iparams), sp or b"\0", len(sparams), blob, len(blob),
                                       gens_capacity, label, len(label), b"".join(_sc(v) for v in values), b"".join(_sc(v) for v in blindings),
                                       m, rng_seed, proof, len(proof), ctypes.byref(plen), comms))
-    return proof.raw[:plen.value], [comms.raw[32 * i:32 * i + 32] for i in range(m)]
+    return proof.raw[:plen.value], [comms.raw[32 * i:32 * i + 32] for i in range(m - gadget_aux_count(name, list(iparams)))]
 
 
 GADGET_EAGER_COMMITS = 1
@@ -732,6 +762,7 @@ def gadget_prove_on(gens, name, iparams, sparams, label, values, blindings, m, b
                                         label, len(label), values or b"\0", blindings or b"\0", m, batch, rng_seeds, proofs, cap, ctypes.byref(plen), comms, sec,
                                         (GADGET_EAGER_COMMITS if eager_commits else 0) | (0 if chain_ahead else GADGET_NO_CHAIN_AHEAD)))
     n, praw, craw = plen.value, proofs.raw, comms.raw
+    m -= gadget_aux_count(name, list(iparams))   # (the lean tree forms: the committed values only, packed per proof)
     return ([praw[i * n:(i + 1) * n] for i in range(batch)],
             [[craw[(i * m + j) * 32:(i * m + j + 1) * 32] for j in range(m)] for i in range(batch)],
             dict(zip(("commit", "gadget", "circuit", "prove", "total"), sec)))

@@ -189,6 +189,7 @@ struct bpr1cs_gens {
 struct bpr1cs_circuit {
     uint32_t n = 0, q = 0, m = 0, N = 1, lgN = 0;
     uint32_t p = 0;   // public inputs per proof (BPR1CS_VAR_PUBLIC): 1 + the highest index a constraint term or linear combination uses
+    uint32_t a = 0;   // auxiliary inputs per proof (BPR1CS_W_AUX): 1 + the highest index an operand of the witness program names
     DevBuf<uint32_t> slot_off, ent_row, chunk_lo, slot_chunk;
     std::vector<uint32_t> h_slot_chunk;  // host copy: first chunk of every slot
     DevBuf<sc> ent_coeff;

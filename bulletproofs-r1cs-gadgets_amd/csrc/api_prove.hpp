@@ -183,9 +183,11 @@ static void enqueue_witness_check(const bpr1cs_circuit* c, const sc* W, const sc
 static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const strobe* init, size_t n_init, bool want_tr,
                            const uint8_t* values, const uint8_t* v_blindings, const uint8_t* rng_seeds,
                            const uint8_t* wires, size_t batch, bpr1cs_job** job_out, const uint8_t* ext_draws = nullptr, int auto_share = 0,
-                           bool first_of_call = false, const uint8_t* publics = nullptr) {
+                           bool first_of_call = false, const uint8_t* publics = nullptr, const uint8_t* aux = nullptr) {
     // publics: this job's part of the public block - batch x p x 32, proof-major; nullptr = the block lies behind the job's own
     // committed values (the caller handed in `values` of exactly this batch: bpr1cs_prove_batch_begin)
+    // aux: this job's part of the auxiliary block - batch x a x 32, proof-major - cut like `publics`; nullptr = behind the job's own public
+    // block.  Read only when the device program runs: with host wires the block may be absent
     // ext_draws (bpr1cs_prove_batch_draws): the caller has appended Prover::new's and commit's transcript messages and "m" itself - `init` holds
     // one transcript per proof in that state - and has run the proof's TranscriptRng: batch x (2n + 8) raw 64-byte draws
     if (!g || !c || !init || (!rng_seeds && !ext_draws) || !job_out || batch == 0 || (n_init != 1 && n_init != batch)) return BPR1CS_ERR_INVALID_ARGUMENT;
@@ -195,15 +197,21 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
         if (!values) return BPR1CS_ERR_INVALID_ARGUMENT;
         publics = values + batch * (size_t)c->m * 32;
     }
+    const uint32_t na = wires ? 0u : c->a;   // auxiliary rows of this job
+    if (na && !aux) {
+        if (!values) return BPR1CS_ERR_INVALID_ARGUMENT;
+        aux = values + batch * (size_t)(c->m + c->p) * 32;
+    }
     if (!have_device()) return BPR1CS_ERR_NO_DEVICE;
     if (g->cap < c->N) return BPR1CS_ERR_INVALID_GENERATORS_LENGTH;
     if (!wires && !c->has_program) return BPR1CS_ERR_MISSING_ASSIGNMENT;
     // the largest grid of a JOB must fit 2^32 threads (N = 32768: 26 000 proofs; bpr1cs_prove_batch cuts larger batches into jobs)
-    if (batch > (1u << 20) || ((uint64_t)4 * c->N + 3ull * c->n + c->m + c->p + 64) * batch > 0xffffffffull) return BPR1CS_ERR_INVALID_ARGUMENT;
+    if (batch > (1u << 20) || ((uint64_t)4 * c->N + 3ull * c->n + c->m + c->p + c->a + 64) * batch > 0xffffffffull) return BPR1CS_ERR_INVALID_ARGUMENT;
     // Scalar inputs are canonical encodings (Scalar::to_bytes); anything else is refused here
     if (c->m && (!host_scalars_canonical(values, batch * c->m) || !host_scalars_canonical(v_blindings, batch * c->m))) return BPR1CS_ERR_INVALID_ARGUMENT;
     if (wires && !host_scalars_canonical(wires, batch * 3 * (size_t)c->n)) return BPR1CS_ERR_INVALID_ARGUMENT;
     if (c->p && !host_scalars_canonical(publics, batch * c->p)) return BPR1CS_ERR_INVALID_ARGUMENT;
+    if (na && !host_scalars_canonical(aux, batch * na)) return BPR1CS_ERR_INVALID_ARGUMENT;
     bpr1cs_job* job = nullptr;
     struct Scope {  // every buffer released while enqueuing stays alive until the job has drained
         std::vector<void*>* prev;
@@ -250,8 +258,9 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     // everything the caller hands over but the wires in ONE pinned block and ONE copy: committed values and blindings (element-major
     // [m][B]), the outside randomness, the transcripts the proofs start from.  (Four synchronous copies of a few hundred bytes each were
     // 0.1 ms in front of a 64-bit bound check's 3 ms.)
-    // (public inputs, when the circuit has any: element-major [p][B] like the values, at the end of the block)
-    const size_t vb = (size_t)m * B * sizeof(sc), sb = (size_t)B * 32, ib = n_init * sizeof(strobe), ub = (size_t)np * B * sizeof(sc);
+    // (public inputs, when the circuit has any: element-major [p][B] like the values, at the end of the block; behind them the auxiliary
+    // inputs of a job the device program synthesises, [a][B]: the two are ONE run of np + na value rows)
+    const size_t vb = (size_t)m * B * sizeof(sc), sb = (size_t)B * 32, ib = n_init * sizeof(strobe), ub = (size_t)(np + na) * B * sizeof(sc);
     job->h_in_bytes = 2 * vb + sb + ib + ub;
     job->h_in = (uint8_t*)host_stage_alloc(job->h_in_bytes);
     {
@@ -267,6 +276,9 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
         sc* hu = (sc*)(job->h_in + 2 * vb + sb + ib);
         for (size_t b = 0; b < B; b++)
             for (size_t k = 0; k < np; k++) hu[k * B + b] = sc_load_raw(publics + (b * np + k) * 32);
+        sc* ha = hu + (size_t)np * B;
+        for (size_t b = 0; b < B; b++)
+            for (size_t k = 0; k < na; k++) ha[k * B + b] = sc_load_raw(aux + (b * na + k) * 32);
     }
     DevBuf<uint8_t> d_in(job->h_in_bytes);
     dev_h2d_async(d_in.p, job->h_in, job->h_in_bytes, sl);
@@ -274,11 +286,12 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     sc* vbl_raw = (sc*)d_in.p + (size_t)m * B;
     uint8_t* d_seeds = d_in.p + 2 * vb;
     strobe* d_init = (strobe*)(d_in.p + 2 * vb + sb);
-    // v_m: the committed values and, in rows m .. m+p-1, the public inputs - the value rows the witness program and the witness check read
-    DevBuf<sc> v_m((size_t)(m + np) * B), vbl_m((size_t)m * B);
+    // v_m: the committed values and, in rows m .. m+p-1, the public inputs - the value rows the witness program and the witness check read -
+    // and, in rows m+p .. m+p+a-1, the auxiliary inputs, which only the witness program reads (constraints cannot address them)
+    DevBuf<sc> v_m((size_t)(m + np + na) * B), vbl_m((size_t)m * B);
     const uint32_t init_stride = n_init == 1 ? 0u : 1u;
     launch((uint64_t)m * B, K_load_inputs{v_raw, vbl_raw, v_m.p, vbl_m.p}, sl);
-    if (np) launch((uint64_t)np * B, K_load_wires{(const sc*)(d_in.p + 2 * vb + sb + ib), v_m.p + (size_t)m * B}, sl);
+    if (np + na) launch((uint64_t)(np + na) * B, K_load_wires{(const sc*)(d_in.p + 2 * vb + sb + ib), v_m.p + (size_t)m * B}, sl);
 
     DBG_JOB("begin: inputs uploaded");
     // ---- P1: V commitments, transcript, RNG stream
@@ -726,7 +739,7 @@ static uint32_t auto_job_proofs(const bpr1cs_gens* g, const bpr1cs_circuit* c, b
     const size_t Mr = N >> r, nfl = c->h_slot_chunk.empty() ? 0 : c->h_slot_chunk[3 * n + m];
     const size_t tail_m = std::min<size_t>(N, 128);
     const size_t front_shared = 160 * n + 64 * (2 * n + 7);   // W and the raw TranscriptRng output: ONE copy for the jobs in flight
-    const size_t front = 200 * m + 64 * (size_t)c->p + 4 * 32 * (size_t)c->px_stride + 512 + c->lgN * 128 +   // (public inputs: raw and Montgomery form)
+    const size_t front = 200 * m + 64 * ((size_t)c->p + c->a) + 4 * 32 * (size_t)c->px_stride + 512 + c->lgN * 128 +   // (public and auxiliary inputs: raw and Montgomery form)
                          tail_m * (2 * 32 + 2 * sizeof(ge)) + (tail_m / 2) * (4 * VB_MULT * sizeof(ge_cached) + 4 * VB_WORDS * 4) + 2 * VB_WINDOWS * 5 * sizeof(ge);
     const size_t others = 32 * (3 * n + m + nfl) + 64 * N, vt = r < c->lgN ? (size_t)VB_MULT * 4 * std::max<size_t>(1, Mr / 2) * sizeof(ge_cached) : 0;
     const size_t back = std::max(others, vt) + 64 * N + 2 * VB_WINDOWS * sizeof(ge) + 30000;   // (folded generators, digits, window sums: inside the dead rows of l / r)
@@ -743,7 +756,7 @@ static uint32_t auto_job_proofs(const bpr1cs_gens* g, const bpr1cs_circuit* c, b
     }
     const size_t avail = dev_free_memory() + g->arena.bytes() + g->front[0].bytes() + g->front[1].bytes() + g->shared_front.bytes();
     const size_t reserve = (size_t)4 << 30;   // what must stay free at the peak (the HIP runtime's own needs, another handle's small jobs)
-    const uint64_t grid_per_proof = (uint64_t)4 * c->N + 3ull * c->n + c->m + c->p + 64;
+    const uint64_t grid_per_proof = (uint64_t)4 * c->N + 3ull * c->n + c->m + c->p + c->a + 64;
     // (small circuits: measured 104 k / 116 k / 126 k / 128 k proofs/s at 4096 / 8192 / 16384 / 32768 proofs per job for the 2:1 Poseidon
     // preimage circuit, 62.8 k / 69.0 k / 71.6 k / 70.5 k for MiMC + set membership)
     if (why) { why->avail = avail; why->per_proof = (uint64_t)front * in_flight + front_shared + back; why->fixed = fixed + reserve; }
@@ -769,7 +782,7 @@ static int prove_batch_impl(const bpr1cs_gens* g, const bpr1cs_circuit* c, const
     bpr1cs_prove_stats acc{};
     const int depth = g->opts.jobs_in_flight.load() == 1 ? 1 : 2;
     size_t J = (size_t)g->opts.job_proofs.load();
-    const uint64_t grid_per_proof = (uint64_t)4 * c->N + 3ull * c->n + c->m + c->p + 64;
+    const uint64_t grid_per_proof = (uint64_t)4 * c->N + 3ull * c->n + c->m + c->p + c->a + 64;
     const size_t grid_max = (size_t)std::min<uint64_t>(0xffffffffull / grid_per_proof, 1u << 20);
     if (grid_max == 0) return BPR1CS_ERR_INVALID_ARGUMENT;
     const bool automatic = J == 0;
@@ -802,6 +815,10 @@ static int prove_batch_impl(const bpr1cs_gens* g, const bpr1cs_circuit* c, const
     // public inputs: the tail block of `values`, behind the committed values of the WHOLE batch; cut per job like them
     if (c->p && !values) return BPR1CS_ERR_INVALID_ARGUMENT;
     const uint8_t* publics = c->p ? values + batch * m * 32 : nullptr;
+    // auxiliary inputs: the block behind them, read only when the device program synthesises the wires
+    const size_t na = wires ? 0 : c->a;
+    if (na && !values) return BPR1CS_ERR_INVALID_ARGUMENT;
+    const uint8_t* aux = na ? values + batch * (m + c->p) * 32 : nullptr;
     struct Pending { bpr1cs_job* job; size_t first; };
     std::vector<Pending> fl;
     int rc = BPR1CS_OK;
@@ -854,7 +871,7 @@ static int prove_batch_impl(const bpr1cs_gens* g, const bpr1cs_circuit* c, const
                                  values ? values + done * m * 32 : nullptr, v_blindings ? v_blindings + done * m * 32 : nullptr,
                                  rng_seeds ? rng_seeds + done * 32 : nullptr, wires ? wires + done * wn * 32 : nullptr, take, &job,
                                  ext_draws ? ext_draws + done * (2 * (size_t)c->n + 8) * 64 : nullptr, auto_share(take), fl.empty(),
-                                 publics ? publics + done * (size_t)c->p * 32 : nullptr);
+                                 publics ? publics + done * (size_t)c->p * 32 : nullptr, aux ? aux + done * na * 32 : nullptr);
         if (e == BPR1CS_ERR_OUT_OF_MEMORY && (take > 64 || !retried)) {
             // out of memory: let the jobs in flight finish and hand the scratch back (arenas sized for the smaller jobs of an
             // earlier call sit next to the blocks that replace them until their last user has drained) - then the same job once

@@ -172,6 +172,10 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
     // silently oblige every prove and verify call to carry values nothing reads
     const uint32_t PUBLIC_MAX = 1u << 20;
     uint32_t npub = 0;
+    // auxiliary inputs (BPR1CS_W_AUX): a = 1 + the highest index an operand of the witness program names.  An operand kind only: a
+    // constraint term or a combination whose variable carries a kind above BPR1CS_VAR_PUBLIC is refused like any unknown variable kind (var_ok, slot_of)
+    const uint32_t AUX_MAX = 1u << 20;
+    uint32_t naux = 0;
     auto public_term_ok = [&](uint32_t var, const uint8_t* coeff) { return (var >> 28) != VK_PUBLIC || !sc_is_zero(host_mont(coeff)); };
     auto var_ok = [&](uint32_t var, uint32_t wire_limit) {  // wire_limit: multipliers a reference may point at
         uint32_t kind = var >> 28, idx = var & 0x0fffffffu;
@@ -204,6 +208,8 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
                 return true;
             }
             if (kind == WK_INV_LEFT) return right;
+            // auxiliary input k of this proof (either side; a = 1 + the highest k sizes the third block of the prove calls' `values`)
+            if (kind == BPR1CS_W_AUX) { if (arg >= AUX_MAX) return false; naux = std::max(naux, arg + 1); return true; }
             if (kind == WK_BIT || kind == WK_NOTBIT) return (arg >> 8) < d->m;  // any of the 256 bits of the canonical value (the as-shipped depth-128 tree takes 2 x 128)
             return false;
         };
@@ -224,7 +230,7 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
     bpr1cs_circuit* c = nullptr;
     API_TRY
     c = new bpr1cs_circuit();
-    c->n = d->n; c->q = d->q; c->m = d->m; c->p = npub;
+    c->n = d->n; c->q = d->q; c->m = d->m; c->p = npub; c->a = d->wops ? naux : 0;
     c->N = 1; c->lgN = 0;
     while (c->N < d->n) { c->N <<= 1; c->lgN++; }
     dev_stream_t s{};
@@ -311,8 +317,13 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
         c->has_program = true;
         std::vector<WOp> ops(d->n);
         // (the caller's kinds 4 and 5 are WK_VAR and WK_ZERO in here: the bit-of-a-combination kinds get internal numbers of their own)
-        auto internal_kind = [](uint32_t kind) { return kind == BPR1CS_W_LCBIT ? WK_LCBIT : kind == BPR1CS_W_LCNOTBIT ? WK_LCNOTBIT : kind; };
-        for (uint32_t i = 0; i < d->n; i++) ops[i] = WOp{internal_kind(d->wops[i].lkind), d->wops[i].larg, internal_kind(d->wops[i].rkind), d->wops[i].rarg};
+        // (the caller's BPR1CS_W_AUX has no internal number of its own: an auxiliary input is a plain read of value row m + p + k - the prove job
+        // lays the auxiliary block behind the public inputs in v_m - so it leaves here as the WK_VAR a {1 * Committed} combination becomes)
+        auto internal_kind = [](uint32_t kind) { return kind == BPR1CS_W_LCBIT ? WK_LCBIT : kind == BPR1CS_W_LCNOTBIT ? WK_LCNOTBIT : kind == BPR1CS_W_AUX ? WK_VAR : kind; };
+        auto internal_arg = [&](uint32_t kind, uint32_t arg) { return kind == BPR1CS_W_AUX ? (VK_COMMITTED << 28) | (d->m + npub + arg) : arg; };
+        for (uint32_t i = 0; i < d->n; i++)
+            ops[i] = WOp{internal_kind(d->wops[i].lkind), internal_arg(d->wops[i].lkind, d->wops[i].larg),
+                         internal_kind(d->wops[i].rkind), internal_arg(d->wops[i].rkind, d->wops[i].rarg)};
         uint32_t nt = d->n_lc ? d->lc_off[d->n_lc] : 0;
         std::vector<uint32_t> lo(d->lc_off, d->lc_off + d->n_lc + 1), lv(d->lc_var, d->lc_var + nt);
         // a public input is a read of value row m + k: the prove job lays the public block behind the committed values (v_m), and

@@ -203,6 +203,7 @@ bpr1cs_circuit* CircuitCompiler::finish(uint32_t* n_out, uint32_t* q_out, uint32
                 case WitnessHint::InverseOfLeft: kind = BPR1CS_W_INV_LEFT; arg = 0; break;
                 case WitnessHint::Bit: kind = BPR1CS_W_BIT; arg = (h.committed << 8) | h.bit; break;
                 case WitnessHint::NotBit: kind = BPR1CS_W_NOTBIT; arg = (h.committed << 8) | h.bit; break;
+                case WitnessHint::Aux: kind = BPR1CS_W_AUX; arg = h.aux; break;
                 default: kind = BPR1CS_W_LC; arg = add_lc(LinearCombination());
             }
         };
@@ -257,6 +258,9 @@ struct Harness {
     std::function<Variable(size_t k)> commit;
     std::function<std::optional<Scalar>(size_t k)> value;    // assignment of the k-th committed value
     std::function<std::optional<uint64_t>(size_t k)> value64;
+    // true: the caller's list holds the COMMITTED values only (the verify entry points), so a gadget that allocates some of its
+    // high-level values ("vsmt_4_aux", "vsmt_2_aux") commits the ones behind them at their position in that list
+    bool packed = false;
 };
 
 struct GadgetSpec {
@@ -273,6 +277,26 @@ static uint64_t u64_of(const std::vector<uint32_t>& ip, size_t i) { return (uint
 static size_t run_gadget(const GadgetSpec& g, Harness& h) {
     auto AS = [&](size_t k) { return AllocatedScalar{h.commit(k), h.value(k)}; };
     auto AQ = [&](size_t k) { return AllocatedQuantity{h.commit(k), h.value64(k)}; };
+    // high-level values first .. first + count - 1 as ALLOCATED wires instead of commitments (BPR1CS_W_AUX, include/bpr1cs.h "Auxiliary
+    // inputs"): consecutive values are paired by allocate_multiplier((v_k, v_k+1)) with the hints Aux(j), Aux(j + 1), j counting the
+    // auxiliary values in gadget order; an odd count ends with (v_k, 0), whose right hint is the empty combination.  No allocate_single:
+    // the pairing is explicit, so that a harness in another language allocates the same multipliers
+    uint32_t aux_next = 0;
+    auto allocated = [&](size_t first, size_t count) {
+        std::vector<AllocatedScalar> out;
+        for (size_t i = 0; i < count; i += 2) {
+            const bool pair = i + 1 < count;
+            const std::optional<Scalar> l = h.value(first + i), r = pair ? h.value(first + i + 1) : std::optional<Scalar>(Scalar());
+            std::optional<std::pair<Scalar, Scalar>> asg;
+            if (l && r) asg = std::make_pair(*l, *r);
+            MulVars mv = h.cs.allocate_multiplier(asg, WitnessHint::aux_input(aux_next),
+                                                  pair ? WitnessHint::aux_input(aux_next + 1) : WitnessHint::of_lc(LinearCombination()));
+            out.push_back(AllocatedScalar{mv.left, l});
+            if (pair) out.push_back(AllocatedScalar{mv.right, r});
+            aux_next += pair ? 2 : 1;
+        }
+        return out;
+    };
     if (g.name == "factors") {  // src/factors.rs:48-103
         auto p = AS(0), q = AS(1);
         factors(h.cs, p, q, g.sp.at(0));
@@ -412,24 +436,33 @@ static size_t run_gadget(const GadgetSpec& g, Harness& h) {
     const bool root_public = g.sp.empty() && dynamic_cast<CircuitCompiler*>(&h.cs) != nullptr;
     const Variable* pub_root = root_public ? &pub0 : nullptr;
     const Scalar no_root;
-    if (g.name == "vsmt_4") {  // src/gadget_vsmt_4.rs:363-440 ; ip = [levels, partial_rounds(, sbox)], sp = [root] (compiled: [] = public root)
+    // "vsmt_4_aux" / "vsmt_2_aux": the same statements with the proof nodes - which link to nothing outside the proof - allocated, not
+    // committed: m = 4 instead of 4 + 3 levels, m = 5 + depth instead of 5 + 2 depth.  ip, sp, the public-root rule and the high-level
+    // values are those of the plain gadgets; leaf, index (bits) and statics are committed in the same order
+    if (g.name == "vsmt_4" || g.name == "vsmt_4_aux") {  // src/gadget_vsmt_4.rs:363-440 ; ip = [levels, partial_rounds(, sbox)], sp = [root] (compiled: [] = public root)
         size_t levels = g.ip.at(0);
         PoseidonParams params(6, 4, 4, g.ip.at(1), g.blob, g.blob_len);
         auto leaf = AS(0), idx = AS(1);
         std::vector<AllocatedScalar> nodes;
+        const bool lean = g.name == "vsmt_4_aux";
+        if (lean) nodes = allocated(2, 3 * levels);
+        else
         for (size_t i = 0; i < 3 * levels; i++) nodes.push_back(AS(2 + i));
-        auto st = statics_from(2 + 3 * levels, 2);
+        auto st = statics_from(2 + (lean && h.packed ? 0 : 3 * levels), 2);
         vanilla_merkle_merkle_tree_4_verif_gadget(h.cs, levels, root_public ? no_root : g.sp.at(0), leaf, idx, nodes, st, params, levels / 4, tree_sbox(), pub_root);
         return 4 + 3 * levels;
     }
-    if (g.name == "vsmt_2") {  // src/gadget_vsmt_2.rs:262-352 ; ip = [depth, partial_rounds(, sbox)], sp = [root] (compiled: [] = public root)
+    if (g.name == "vsmt_2" || g.name == "vsmt_2_aux") {  // src/gadget_vsmt_2.rs:262-352 ; ip = [depth, partial_rounds(, sbox)], sp = [root] (compiled: [] = public root)
         size_t depth = g.ip.at(0);
         PoseidonParams params(6, 4, 4, g.ip.at(1), g.blob, g.blob_len);
         auto leaf = AS(0);
         std::vector<AllocatedScalar> bits, nodes;
         for (size_t i = 0; i < depth; i++) bits.push_back(AS(1 + i));
+        const bool lean = g.name == "vsmt_2_aux";
+        if (lean) nodes = allocated(1 + depth, depth);
+        else
         for (size_t i = 0; i < depth; i++) nodes.push_back(AS(1 + depth + i));
-        auto st = statics_from(1 + 2 * depth, 4);
+        auto st = statics_from(1 + depth + (lean && h.packed ? 0 : depth), 4);
         vanilla_merkle_merkle_tree_verif_gadget(h.cs, depth, root_public ? no_root : g.sp.at(0), leaf, bits, nodes, st, params, tree_sbox(), pub_root);
         return 5 + 2 * depth;
     }
@@ -618,7 +651,7 @@ int bpr1cs_gadget_prove_on_flags(const bpr1cs_gens* gens, const char* gadget, co
                     prover.export_csr(row_off, tvar, tcoeff);
                     bpr1cs_circuit_desc d{};
                     n0 = prover.a_L.size(); q0 = prover.constraints.size();
-                    d.n = (uint32_t)n0; d.q = (uint32_t)q0; d.m = (uint32_t)m;
+                    d.n = (uint32_t)n0; d.q = (uint32_t)q0; d.m = (uint32_t)prover.v_.size();   // (the values the gadget COMMITTED: fewer than m for "vsmt_4_aux" / "vsmt_2_aux")
                     d.row_off = row_off.data(); d.term_var = tvar.data(); d.term_coeff = tcoeff.data();
                     int rc = bpr1cs_circuit_create(&d, &c);
                     if (rc) throw R1CSError::Backend(rc);
@@ -744,6 +777,7 @@ int bpr1cs_gadget_verify_single(const char* gadget, const uint32_t* iparams, siz
                       return verifier.commit(c);
                   },
                   [](size_t) { return std::optional<Scalar>(); }, [](size_t) { return std::optional<uint64_t>(); }};
+        h.packed = true;
         run_gadget(g, h);
         R1CSProof p = R1CSProof::from_bytes(proof, proof_len);  // FormatError: bad version / length / non-canonical scalar
         verifier.verify(p, pc_gens, bp_gens, nullptr);          // the verifier's r from fresh randomness (rand::thread_rng upstream)
@@ -778,6 +812,7 @@ int bpr1cs_gadget_verify_on(const bpr1cs_gens* gens, const char* gadget, const u
                       return verifier.commit(c);
                   },
                   [](size_t) { return std::optional<Scalar>(); }, [](size_t) { return std::optional<uint64_t>(); }};
+        h.packed = true;
         run_gadget(g, h);
         sec[0] = now_s() - t_start;
         int rc = BPR1CS_OK;

@@ -267,13 +267,17 @@ struct AllocatedScalar {
 // Extension over the reference API (default = none): gadgets that pass hints can be
 // compiled into a device witness program; without hints the Prover path still works.
 struct WitnessHint {
-    enum Kind { None, LC, InverseOfLeft, Bit, NotBit, LcBit, LcNotBit } kind = None;
+    enum Kind { None, LC, InverseOfLeft, Bit, NotBit, LcBit, LcNotBit, Aux } kind = None;
     LinearCombination lc;       // LC, LcBit / LcNotBit
     uint32_t committed = 0;     // Bit / NotBit: index of the committed value
     uint32_t bit = 0;
+    uint32_t aux = 0;           // Aux: index of the auxiliary input
     const void* lc_object = nullptr;   // LcBit / LcNotBit: the combination object handed in (CircuitCompiler: one `lc` entry per object)
     static WitnessHint of_lc(const LinearCombination& l) { WitnessHint h; h.kind = LC; h.lc = l; return h; }
     static WitnessHint inverse_of_left() { WitnessHint h; h.kind = InverseOfLeft; return h; }
+    // a wire the prover chooses freely: auxiliary input k of the proof at hand (BPR1CS_W_AUX).  The Prover takes the assignment, the
+    // Verifier allocates; only the CircuitCompiler reads the index
+    static WitnessHint aux_input(uint32_t k) { WitnessHint h; h.kind = Aux; h.aux = k; return h; }
     static WitnessHint bit_of(const Variable& v, uint32_t k, bool negate) {
         WitnessHint h;
         h.kind = negate ? NotBit : Bit;

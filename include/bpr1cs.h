@@ -112,6 +112,26 @@ typedef struct bpr1cs_circuit bpr1cs_circuit; /* the constraint system a Prover 
 #define BPR1CS_W_NOTBIT 3u   /* 1 - that bit */
 #define BPR1CS_W_LCBIT 4u    /* bit (arg & 0xff) of the canonical value x, 0 <= x < l, of linear combination #(arg >> 8) */
 #define BPR1CS_W_LCNOTBIT 5u /* 1 - that bit */
+#define BPR1CS_W_AUX 10u     /* auxiliary input #arg of THIS proof: a wire the prover chooses freely (see "Auxiliary inputs" below); operand
+                                kinds 6 .. 9 are not part of the ABI and stay BPR1CS_ERR_INVALID_ARGUMENT, as they always were */
+/* Auxiliary inputs.  A wire the prover assigns without deriving it from anything - upstream's `cs.allocate(Some(x))` and
+ * `allocate_multiplier(Some((l, r)))`: the nodes of a Merkle path, which link to nothing outside the proof - need not be a Pedersen
+ * commitment for the device program to know it: an operand (BPR1CS_W_AUX, k) stands for a_k, the k-th auxiliary input of the proof at
+ * hand.  Either side of any multiplier may be one; BPR1CS_W_INV_LEFT on the right of a BPR1CS_W_AUX left is allowed.  It is an OPERAND
+ * kind only: linear combinations and bit operands reach the value through the wire it was written to (wires of EARLIER multipliers,
+ * as always), and a variable of kind 6 or above in `term_var` or `lc_var` stays BPR1CS_ERR_INVALID_ARGUMENT - an auxiliary value is not a variable.
+ * bpr1cs_circuit_create derives a = 1 + the highest index the operands of `wops` name (a <= 2^20: an index >= 2^20 is
+ * BPR1CS_ERR_INVALID_ARGUMENT; a = 0 when the kind does not occur or the description has no `wops`, and then every call is exactly
+ * what it was).  Indices below a that no operand names are allowed - the caller still supplies them - and several operands may name
+ * one index.  No entry point reports a: a caller derives it from its own description by the same rule.
+ * The values ride in the array the prove calls already take, as one more tail block:
+ *   prove calls   `values`      = batch x m x 32 committed values, then batch x p x 32 public inputs, then batch x a x 32 auxiliary
+ *                 inputs, proof-major, canonical  (bpr1cs_prove_batch, _transcripts, _draws, _begin; v_blindings, commitments_out,
+ *                 transcripts: over the m committed values only, as before)
+ * The block is read only when the device program runs (wires == NULL): with host wires it is not read and may be absent.  a > 0 with
+ * wires == NULL and values == NULL, and a non-canonical auxiliary scalar, are BPR1CS_ERR_INVALID_ARGUMENT (like every scalar input of
+ * the prover).  The verify calls never see the block: the verifier allocates the wire and learns nothing of its value.  Auxiliary
+ * inputs are secrets and are wiped wherever committed values are. */
 /* BPR1CS_W_LCBIT / BPR1CS_W_LCNOTBIT give the bits of a DERIVED value - v - min, a product wire, a hash output, v - Public(0) - so that
  * a range check needs no commitment beside v.  Either may be a left or a right operand.  The combination index is < n_lc (and < 2^24:
  * it shares `arg` with the bit index); the combination may read what a BPR1CS_W_LC operand of the same multiplier may read - committed
@@ -332,7 +352,8 @@ size_t bpr1cs_proof_len(const bpr1cs_circuit* c);
 /* Batched Prover::commit x m  +  gadget synthesis  +  Prover::prove
  * (reference src/gadget_vsmt_4.rs:390-434), one independent transcript per proof.
  *   label              Transcript::new(label)
- *   values             batch * m * 32   committed values, proof-major (+ batch * p * 32 public inputs behind them, see "Public inputs")
+ *   values             batch * m * 32   committed values, proof-major (+ batch * p * 32 public inputs behind them, see "Public inputs";
+ *                                       + batch * a * 32 auxiliary inputs behind those when wires == NULL, see "Auxiliary inputs")
  *   v_blindings        batch * m * 32
  *   rng_seeds          batch * 32       the 32 bytes upstream draws from thread_rng()
  *                                       in TranscriptRng::finalize (made explicit)
