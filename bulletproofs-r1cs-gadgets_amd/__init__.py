@@ -18,6 +18,7 @@ POSEIDON_PARAMS_PATH = os.path.join(_HERE, "data", "poseidon_params_ristretto.bi
 
 VAR_COMMITTED, VAR_MUL_LEFT, VAR_MUL_RIGHT, VAR_MUL_OUT, VAR_ONE = 0, 1, 2, 3, 4
 VAR_PUBLIC = 5   # public input k of the proof at hand (include/bpr1cs.h "Public inputs"): its value rides in the calls' `publics`
+VAR_SCALE = 8    # a marker, not a term: the term that follows it has its coefficient multiplied by public input k (include/bpr1cs.h "Public coefficients")
 W_LC, W_INV_LEFT, W_BIT, W_NOTBIT = 0, 1, 2, 3
 W_AUX = 10  # auxiliary input #arg of the proof at hand (include/bpr1cs.h "Auxiliary inputs"): its value rides in the prove calls' `aux`
 W_LCBIT, W_LCNOTBIT = 4, 5    # bit (arg & 0xff) of the canonical value of linear combination #(arg >> 8); 1 - that bit
@@ -238,10 +239,21 @@ class Gens:
             pass
 
 
+def _emit_term(term, var, coeff):
+    """((kind, idx), c) -> one entry; ((kind, idx), c, k) -> the marker (VAR_SCALE << 28 | k, 1) and the entry"""
+    if len(term) == 3:
+        var.append((VAR_SCALE << 28) | term[2])
+        coeff += (1).to_bytes(32, "little")
+    (kind, idx), c = term[0], term[1]
+    var.append((kind << 28) | idx)
+    coeff += c if isinstance(c, (bytes, bytearray)) else int(c).to_bytes(32, "little")
+
+
 class Circuit:
     """Flattened constraint system (+ optional device witness program).
 
-    constraints: list of rows, each a list of ((kind, index), coeff_int_or_bytes); kind VAR_PUBLIC = public input `index`
+    constraints: list of rows, each a list of ((kind, index), coeff_int_or_bytes); kind VAR_PUBLIC = public input `index`;
+    a term ((kind, index), coeff, k) has the public coefficient coeff x p_k (emitted as a VAR_SCALE marker with coefficient 1 + the term)
     wops: optional list of (lkind, larg, rkind, rarg); lcs: list of term lists for W_LC / W_LCBIT / W_LCNOTBIT operands.
     .p: public inputs per proof (1 + the highest index used, as the library derives it; raw=: scanned from the variable list).
     .a: auxiliary inputs per proof (1 + the highest index a W_AUX operand of `wops` names, as the library derives it; 0 without wops).
@@ -255,14 +267,16 @@ class Circuit:
         else:
             row_off, tvar, tcoef = [0], [], bytearray()
             for row in constraints:
-                for (kind, idx), c in row:
-                    tvar.append((kind << 28) | idx)
-                    tcoef += c if isinstance(c, (bytes, bytearray)) else int(c).to_bytes(32, "little")
+                for term in row:
+                    _emit_term(term, tvar, tcoef)
                 row_off.append(len(tvar))
             q = len(constraints)
         self.q = q
-        pub = [v & 0x0fffffff for v in tvar if v >> 28 == VAR_PUBLIC]
-        pub += [idx for terms in (lcs or []) if wops is not None for (kind, idx), _ in terms if kind == VAR_PUBLIC]
+        pub = [v & 0x0fffffff for v in tvar if v >> 28 in (VAR_PUBLIC, VAR_SCALE)]
+        for terms in (lcs or []) if wops is not None else []:
+            for term in terms:
+                pub += [term[0][1]] if term[0][0] in (VAR_PUBLIC, VAR_SCALE) else []
+                pub += [term[2]] if len(term) == 3 else []
         self.p = 1 + max(pub) if pub else 0
         aux = [arg for w in (wops or []) for kind, arg in ((w[0], w[1]), (w[2], w[3])) if kind == W_AUX]
         self.a = 1 + max(aux) if aux else 0
@@ -274,9 +288,8 @@ class Circuit:
             arr = (_WOp * max(1, len(wops)))(*[_WOp(*w) for w in wops])
             lc_off, lc_var, lc_coeff = [0], [], bytearray()
             for terms in (lcs or []):
-                for (kind, idx), c in terms:
-                    lc_var.append((kind << 28) | idx)
-                    lc_coeff += c if isinstance(c, (bytes, bytearray)) else int(c).to_bytes(32, "little")
+                for term in terms:
+                    _emit_term(term, lc_var, lc_coeff)
                 lc_off.append(len(lc_var))
             self._keep += [arr, _u32arr(lc_off), _u32arr(lc_var), bytes(lc_coeff) or b"\0"]
             d.wops, d.n_lc = arr, len(lcs or [])
@@ -696,7 +709,10 @@ class CompiledGadget:
     circuit then proves and verifies memberships in different trees, `publics` = the roots.  "bound_check_1" (iparams = [bits], ONE
     committed value) compiled without sparams takes its bounds as public inputs 0 and 1 (.p == 2), `publics` = (min, max) per proof.
     "vsmt_4_aux" / "vsmt_2_aux": the tree gadgets with the proof nodes as auxiliary inputs (.a = 3 * levels / depth; .m = 4 / 5 + depth):
-    the prove calls take the nodes as `aux`, the verifiers never see them."""
+    the prove calls take the nodes as `aux`, the verifiers never see them.
+    "set_membership_lean" (iparams = [k]) / "weighted_sum_bound" (iparams = [k, bits]) compiled without sparams take their items /
+    their weights and budget as public inputs, the items and weights as public COEFFICIENTS (.p == k / k + 1): a different set or
+    weight vector per proof on one circuit."""
 
     def __init__(self, name, iparams=(), sparams=(), lib=None, glib=None):
         self.lib = lib or load_library()
@@ -711,6 +727,9 @@ class CompiledGadget:
         self.proof_len = self.lib.bpr1cs_proof_len(h)
         # (host/frontend.cpp run_gadget: the root as Variable::Public(0); the bounds of bound_check_1 as Public(0), Public(1))
         self.p = {"vsmt_4": 1, "vsmt_2": 1, "vsmt_4_aux": 1, "vsmt_2_aux": 1, "bound_check_1": 2}.get(name, 0) if len(sparams) == 0 else 0
+        # (public coefficients: the k items of "set_membership_lean"; the k weights of "weighted_sum_bound" and, as public input k, its budget)
+        if len(sparams) == 0 and name in ("set_membership_lean", "weighted_sum_bound"):
+            self.p = iparams[0] + (1 if name == "weighted_sum_bound" else 0)
         self.a = gadget_aux_count(name, list(iparams))
 
     def close(self):

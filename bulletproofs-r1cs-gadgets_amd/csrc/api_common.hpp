@@ -193,10 +193,16 @@ struct bpr1cs_circuit {
     DevBuf<uint32_t> slot_off, ent_row, chunk_lo, slot_chunk;
     std::vector<uint32_t> h_slot_chunk;  // host copy: first chunk of every slot
     DevBuf<sc> ent_coeff;
+    // public coefficients (BPR1CS_VAR_SCALE): a second CSC over the slots that have scaled entries (K_flatten_scaled_chunks /
+    // K_flatten_scaled) - the arrays above hold the plain entries only.  Empty (n_sc_chunks = 0) for a circuit without a marker.
+    DevBuf<uint32_t> sc_slot, sc_slot_chunk, sc_chunk_lo, sc_ent_row, sc_ent_k;
+    DevBuf<sc> sc_ent_coeff;
+    uint32_t n_sc_slots = 0, n_sc_chunks = 0;
     bool has_program = false;
     DevBuf<WOp> wops;
     DevBuf<uint32_t> lc_off, lc_var;
     DevBuf<sc> lc_coeff;
+    DevBuf<uint32_t> lc_scale;   // beside lc_var, only when a combination holds a scaled term (K_witness_scaled); null otherwise
     // Poseidon permutations evaluated jointly (empty when the description has no usable annotation)
     DevBuf<PoseidonTab> ptab;
     DevBuf<PoseidonPerm> perms;
@@ -241,10 +247,12 @@ struct bpr1cs_circuit {
     // coefficient; chunks of consecutive WHOLE rows (row_chunk[k] = first row of chunk k, closed at CHECK_CHUNK entries).
     std::vector<uint32_t> h_row_off, h_row_slot, h_row_chunk;
     std::vector<sc> h_row_coeff;
+    std::vector<uint32_t> h_row_scale;   // beside h_row_slot, only when the circuit has scaled entries: 0 = plain, 1 + (m + k) = times public input k
+    mutable DevBuf<uint32_t> row_scale;
     mutable DevBuf<uint32_t> row_off, row_slot, row_chunk;
     mutable DevBuf<sc> row_coeff;
     mutable bool rows_uploaded = false;
-    size_t row_form_bytes() const { return h_row_slot.size() * 36 + (h_row_off.size() + h_row_chunk.size()) * 4; }
+    size_t row_form_bytes() const { return h_row_slot.size() * 36 + (h_row_off.size() + h_row_chunk.size() + h_row_scale.size()) * 4; }
     // circuit cache (below): the description this object was built from, and how many handles the callers hold on it
     int cache_refs = -1;   // -1: not in the cache (bpr1cs_circuit_destroy deletes it)
     int cache_device = 0;  // the device its buffers live on

@@ -166,6 +166,7 @@ static void enqueue_witness_check(const bpr1cs_circuit* c, const sc* W, const sc
             upload(c->row_slot, c->h_row_slot, s);
             upload(c->row_coeff, c->h_row_coeff, s);
             upload(c->row_chunk, c->h_row_chunk, s);
+            if (!c->h_row_scale.empty()) upload(c->row_scale, c->h_row_scale, s);
             c->rows_uploaded = true;
         }
     }
@@ -175,7 +176,7 @@ static void enqueue_witness_check(const bpr1cs_circuit* c, const sc* W, const sc
     const uint32_t nchunks = (uint32_t)c->h_row_chunk.size() - 1, per_launch = 0xffffffffu / Bpad;   // (a grid holds 2^32 - 1 threads)
     for (uint32_t c0 = 0; c0 < nchunks; c0 += per_launch)
         launch((uint64_t)std::min(per_launch, nchunks - c0) * Bpad,
-               K_check_rows{c->row_chunk.p, c->row_off.p, c->row_slot.p, c->row_coeff.p, W, v_m, res, B, Bpad, 3 * c->n, c->m + c->p, c0}, s);   // (value rows: committed, then public)
+               K_check_rows{c->row_chunk.p, c->row_off.p, c->row_slot.p, c->row_coeff.p, W, v_m, res, B, Bpad, 3 * c->n, c->m + c->p, c0, c->row_scale.p}, s);   // (value rows: committed, then public)
 }
 
 // One device job.  `init`: the transcripts the proofs start from - n_init = 1 (every proof starts from a copy of init[0]: what
@@ -388,14 +389,24 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
         const dev_stream_t sw = job->st3;
         dev_stream_wait(sw, job->ev_in);
         if (shared) dev_stream_wait(sw, g->w_free_ev);
+        // a circuit whose combinations hold public coefficients (BPR1CS_VAR_SCALE) runs the program's scaled form; every other circuit
+        // launches what it always launched
+        K_witness_scaled kws;
+        static_cast<K_witness&>(kws) = kw;
+        kws.lc_scale = c->lc_scale.p;
 #if defined(BPR1CS_HOSTSIM)
         (void)o_team;
+        if (kws.lc_scale) launch(B, kws, sw); else
         launch(B, kw, sw);   // (a lane per proof: the simulator has no teams)
 #else
         int T = o_team;
         if (c->n_perms && (uint32_t)T < c->macro_width + 2) T = 16;  // poseidon_team needs width + 2 lanes
         kw.prio = 2;  // above the co-resident MSM waves (default 0), below the RNG chain (3)
         const dim3 blocks((uint32_t)(((uint64_t)B * T + 63) / 64));
+        if (kws.lc_scale) {
+            kws.prio = kw.prio;
+            launch_kernel(T == 4 ? k_witness_team_scaled<4> : T == 8 ? k_witness_team_scaled<8> : k_witness_team_scaled<16>, blocks, dim3(64), 0, sw, kws);
+        } else
         launch_kernel(T == 4 ? k_witness_team<4> : T == 8 ? k_witness_team<8> : k_witness_team<16>, blocks, dim3(64), 0, sw, kw);
 #endif
         if (o_check) enqueue_witness_check(c, W.p, v_m.p, chk, B, sw);
@@ -544,7 +555,7 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     // writes at round r, after the launch that materialises the folded generators: 15 of 40 GiB of a 2048-proof job's back phase.
     const uint32_t r_eff = std::min<uint32_t>((uint32_t)o_unfold, lgN);
     const bool fvec = g->opts.factor_vectors.load() == 1;   // factor vectors as arrays (measuring knob); default: closed form, no cG / cH
-    const uint32_t nfl = c->h_slot_chunk[3 * n + m];
+    const uint32_t nfl = flatten_part_chunks(c, 3 * n + m);   // (with public coefficients: the larger of the two passes' chunk counts)
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t w_bytes = al(((size_t)(3 * n + m) * B + 1) * sizeof(sc)), p_bytes = al((size_t)(nfl ? nfl : 1) * B * sizeof(sc)),
                  v_bytes = al((size_t)N * B * sizeof(sc));
@@ -558,7 +569,7 @@ static int prove_job_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const 
     sc* cG = nullptr; sc* cH = nullptr; sc* sG_p = nullptr; sc* sH_p = nullptr;
     if (fvec) { cG = (sc*)nxt; cH = (sc*)(nxt + v_bytes); nxt += 2 * v_bytes; }
     if (need_s) { sG_p = (sc*)nxt; sH_p = (sc*)(nxt + v_bytes); }
-    run_flatten(c, 3 * n + m, plo.p, phi.p, wvec, B, H, st, fpart_p);
+    run_flatten(c, 3 * n + m, plo.p, phi.p, wvec, B, H, st, v_m.p + (size_t)m * B /* the public block: rows m .. m+p-1 */, fpart_p);
     // 4 wavefronts per SIMD: with one (2^16 threads) the kernel is latency bound and a co-running front kernel doubles its time (9 -> 4 ms)
     uint32_t tchunk, TC = pick_chunks(n, B, std::min<uint32_t>(1u << 18, sum_chunk_cap(B, 6) * B), tchunk);
     DevBuf<sc> tpart((size_t)6 * TC * B), tco((size_t)6 * B);
@@ -736,7 +747,7 @@ struct JobSizing { uint64_t avail = 0, per_proof = 0, fixed = 0; };
 static uint32_t auto_job_proofs(const bpr1cs_gens* g, const bpr1cs_circuit* c, bool have_program, int in_flight, JobSizing* why = nullptr) {
     const size_t n = c->n, m = c->m, N = c->N;
     const uint32_t r = eff_unfold(g->opts, 4096, c->lgN);   // (the job sizes considered here are large ones)
-    const size_t Mr = N >> r, nfl = c->h_slot_chunk.empty() ? 0 : c->h_slot_chunk[3 * n + m];
+    const size_t Mr = N >> r, nfl = flatten_part_chunks(c, 3 * n + m);
     const size_t tail_m = std::min<size_t>(N, 128);
     const size_t front_shared = 160 * n + 64 * (2 * n + 7);   // W and the raw TranscriptRng output: ONE copy for the jobs in flight
     const size_t front = 200 * m + 64 * ((size_t)c->p + c->a) + 4 * 32 * (size_t)c->px_stride + 512 + c->lgN * 128 +   // (public and auxiliary inputs: raw and Montgomery form)

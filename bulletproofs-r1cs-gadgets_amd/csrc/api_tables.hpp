@@ -154,8 +154,12 @@ int bpr1cs_gens_point(const bpr1cs_gens* g, int which, uint32_t i, uint8_t out[3
     return BPR1CS_OK;
 }
 
-int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
-    if (!d || !out) return BPR1CS_ERR_INVALID_ARGUMENT;
+int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d0, bpr1cs_circuit** out) {
+    if (!d0 || !out) return BPR1CS_ERR_INVALID_ARGUMENT;
+    // (d0: the caller's description, which the circuit cache hashes and compares; d: the description the rest of this function
+    // reads - the same, or a copy without BPR1CS_VAR_SCALE markers, see below)
+    bpr1cs_circuit_desc eff = *d0;
+    const bpr1cs_circuit_desc* d = &eff;
     if (!have_device()) return BPR1CS_ERR_NO_DEVICE;
     if (d->n > (1u << 24) || d->m > (1u << 20) || d->q > (1u << 26)) return BPR1CS_ERR_INVALID_ARGUMENT;
     if (d->q && (!d->row_off || !d->term_var || !d->term_coeff)) return BPR1CS_ERR_INVALID_ARGUMENT;
@@ -172,6 +176,56 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
     // silently oblige every prove and verify call to carry values nothing reads
     const uint32_t PUBLIC_MAX = 1u << 20;
     uint32_t npub = 0;
+    // public coefficients (BPR1CS_VAR_SCALE): a marker (SCALE << 28 | k, s) in front of a term (var, c) makes the pair the ONE term
+    // s c p_k x var.  The pairs are folded here, before anything else looks at the arrays: the description the code below reads holds
+    // (var, s c) in the pair's place and, beside it, 0 for a plain term and 1 + k for a folded one (tscale / lscale; empty: no marker
+    // anywhere - then `eff` is the caller's description and everything below does what it did).  Refused: a marker at the end of its
+    // row or combination; in front of One, a public term or another marker; k >= 2^20; s or c non-canonical or 0 (as for a public
+    // term: only a term that uses its input may size p).  The marked term's own checks (earlier wires only, committed index < m) are
+    // the unchanged ones further down.
+    struct Folded { std::vector<uint32_t> off, var, scale; std::vector<uint8_t> coeff; bool any = false; };
+    auto fold_markers = [&](uint32_t rows, const uint32_t* off, const uint32_t* var, const uint8_t* coeff, Folded& o) -> bool {
+        const uint32_t nt = rows ? off[rows] : 0;
+        for (uint32_t t = 0; t < nt && !o.any; t++) o.any = (var[t] >> 28) == BPR1CS_VAR_SCALE;
+        if (!o.any) return true;
+        o.off.assign(1, 0);
+        for (uint32_t r = 0; r < rows; r++) {
+            for (uint32_t t = off[r]; t < off[r + 1]; t++) {
+                uint32_t sw = 0;
+                sc co;
+                if ((var[t] >> 28) == BPR1CS_VAR_SCALE) {
+                    const uint32_t k = var[t] & 0x0fffffffu;
+                    if (k >= PUBLIC_MAX || t + 1 >= off[r + 1] || (var[t + 1] >> 28) > VK_OUT) return false;
+                    if (!host_scalars_canonical(coeff + 32 * (size_t)t, 2)) return false;
+                    const sc s_m = host_mont(coeff + 32 * (size_t)t), c_m = host_mont(coeff + 32 * (size_t)(t + 1));
+                    if (sc_is_zero(s_m) || sc_is_zero(c_m)) return false;
+                    co = sc_from_mont(sc_mul(s_m, c_m));   // (a product of two units of a field: never 0)
+                    npub = std::max(npub, k + 1);
+                    sw = k + 1;
+                    t++;
+                } else co = sc_load_raw(coeff + 32 * (size_t)t);   // (as the caller wrote it: reduced where it is read)
+                o.var.push_back(var[t]);
+                o.scale.push_back(sw);
+                static_assert(sizeof(sc) == 32, "a canonical scalar's 32 little-endian bytes are an sc as they are");
+                o.coeff.insert(o.coeff.end(), (const uint8_t*)&co, (const uint8_t*)&co + 32);
+            }
+            o.off.push_back((uint32_t)o.var.size());
+        }
+        return true;
+    };
+    Folded frow, flc;
+    if (d->q) {
+        if (!fold_markers(d->q, d->row_off, d->term_var, d->term_coeff, frow)) return BPR1CS_ERR_INVALID_ARGUMENT;
+        if (frow.any) { eff.row_off = frow.off.data(); eff.term_var = frow.var.data(); eff.term_coeff = frow.coeff.data(); }
+    }
+    if (d->wops && d->n_lc) {
+        if (!d->lc_off || !d->lc_var || !d->lc_coeff || d->lc_off[0] != 0) return BPR1CS_ERR_INVALID_ARGUMENT;
+        for (uint32_t k = 0; k < d->n_lc; k++)
+            if (d->lc_off[k + 1] < d->lc_off[k]) return BPR1CS_ERR_INVALID_ARGUMENT;
+        if (!fold_markers(d->n_lc, d->lc_off, d->lc_var, d->lc_coeff, flc)) return BPR1CS_ERR_INVALID_ARGUMENT;
+        if (flc.any) { eff.lc_off = flc.off.data(); eff.lc_var = flc.var.data(); eff.lc_coeff = flc.coeff.data(); }
+    }
+    const std::vector<uint32_t>&tscale = frow.scale, &lscale = flc.scale;
     // auxiliary inputs (BPR1CS_W_AUX): a = 1 + the highest index an operand of the witness program names.  An operand kind only: a
     // constraint term or a combination whose variable carries a kind above BPR1CS_VAR_PUBLIC is refused like any unknown variable kind (var_ok, slot_of)
     const uint32_t AUX_MAX = 1u << 20;
@@ -224,8 +278,8 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
     const bool cacheable = !d->wops;
     uint64_t cache_key = 0;
     if (cacheable) {
-        cache_key = circuit_desc_hash(d);
-        if (bpr1cs_circuit* hit = circuit_cache_lookup(d, cache_key)) { *out = hit; return BPR1CS_OK; }
+        cache_key = circuit_desc_hash(d0);
+        if (bpr1cs_circuit* hit = circuit_cache_lookup(d0, cache_key)) { *out = hit; return BPR1CS_OK; }
     }
     bpr1cs_circuit* c = nullptr;
     API_TRY
@@ -256,7 +310,7 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
         uint32_t slot;
         int r = slot_of(d->term_var[t], slot);
         if (r < 0) { delete c; return BPR1CS_ERR_INVALID_ARGUMENT; }
-        if (r) cnt[slot + 1]++;
+        if (r && !(frow.any && tscale[t])) cnt[slot + 1]++;   // (a scaled entry goes to the second CSC below)
     }
     for (uint32_t i = 0; i < nslots; i++) cnt[i + 1] += cnt[i];
     std::vector<uint32_t> fill(cnt.begin(), cnt.end() - 1), ent_row(cnt[nslots]);
@@ -265,7 +319,7 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
     for (uint32_t j = 0; j < d->q; j++)
         for (uint32_t t = d->row_off[j]; t < d->row_off[j + 1]; t++) {
             uint32_t slot;
-            if (slot_of(d->term_var[t], slot) == 1) {
+            if (slot_of(d->term_var[t], slot) == 1 && !(frow.any && tscale[t])) {
                 uint32_t p = fill[slot]++;
                 ent_coeff[p] = host_mont(d->term_coeff + 32 * (size_t)t);
                 // (q <= 2^26 was checked above: the two top bits of the row word are free for the +-1 flags of K_flatten_chunks)
@@ -288,11 +342,53 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
         upload(c->slot_chunk, sch, s);
     }
     upload(c->ent_coeff, ent_coeff, s);
+    if (frow.any) {
+        // the scaled entries: by slot (slots < 3n + m: a marker stands in front of a wire or a committed value), within a slot in
+        // ascending row order, cut into chunks of at most FLATTEN_CHUNK for K_flatten_scaled_chunks / K_flatten_scaled
+        std::vector<std::pair<uint32_t, uint32_t>> se;   // (slot, term), sorted by slot; stable: rows stay ascending
+        for (uint32_t t = 0; t < nnz; t++)
+            if (tscale[t]) { uint32_t slot = 0; (void)slot_of(d->term_var[t], slot); se.emplace_back(slot, t); }
+        std::stable_sort(se.begin(), se.end(), [](const std::pair<uint32_t, uint32_t>& a, const std::pair<uint32_t, uint32_t>& b) { return a.first < b.first; });
+        std::vector<uint32_t> term_row(nnz);
+        for (uint32_t j = 0; j < d->q; j++)
+            for (uint32_t t = d->row_off[j]; t < d->row_off[j + 1]; t++) term_row[t] = j;
+        std::vector<uint32_t> sslot, sschunk, sclo, srow(se.size()), sk(se.size());
+        std::vector<sc> scoeff(se.size());
+        for (size_t e = 0; e < se.size(); e++) {
+            const uint32_t t = se[e].second;
+            scoeff[e] = host_mont(d->term_coeff + 32 * (size_t)t);
+            srow[e] = term_row[t] | (memcmp(&scoeff[e], &one_m, sizeof(sc)) == 0 ? 0x80000000u : 0u) |
+                      (memcmp(&scoeff[e], &minus_one_m, sizeof(sc)) == 0 ? 0x40000000u : 0u);
+            sk[e] = tscale[t] - 1;
+        }
+        for (size_t e0 = 0; e0 < se.size();) {
+            size_t e1 = e0;
+            while (e1 < se.size() && se[e1].first == se[e0].first) e1++;
+            sslot.push_back(se[e0].first);
+            sschunk.push_back((uint32_t)sclo.size());
+            for (size_t e = e0; e < e1; e += FLATTEN_CHUNK) sclo.push_back((uint32_t)e);
+            e0 = e1;
+        }
+        sschunk.push_back((uint32_t)sclo.size());
+        c->n_sc_slots = (uint32_t)sslot.size();
+        c->n_sc_chunks = (uint32_t)sclo.size();
+        sclo.push_back((uint32_t)se.size());
+        upload(c->sc_slot, sslot, s);
+        upload(c->sc_slot_chunk, sschunk, s);
+        upload(c->sc_chunk_lo, sclo, s);
+        upload(c->sc_ent_row, srow, s);
+        upload(c->sc_ent_k, sk, s);
+        upload(c->sc_ent_coeff, scoeff, s);
+    }
     {   // the same constraints by row, for K_check_rows (BPR1CS_OPT_CHECK_WITNESS): host copy only, uploaded by the first checked job
         c->h_row_off.assign(1, 0);
         if (d->q) c->h_row_off.assign(d->row_off, d->row_off + d->q + 1);
         c->h_row_slot.resize(nnz);
         c->h_row_coeff.resize(nnz);
+        if (frow.any) {   // K_check_rows: the entry's value times value row m + k (the public block lies behind the committed values in v_m)
+            c->h_row_scale.resize(nnz);
+            for (uint32_t t = 0; t < nnz; t++) c->h_row_scale[t] = tscale[t] ? d->m + tscale[t] : 0u;
+        }
         for (uint32_t t = 0; t < nnz; t++) {
             uint32_t slot = 0;
             (void)slot_of(d->term_var[t], slot);   // (validated by the counting loop above)
@@ -337,7 +433,7 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
             if (kind != WK_LC || arg >= d->n_lc) return;
             uint32_t t0 = lo[arg], t1 = lo[arg + 1];
             if (t1 == t0) { kind = WK_ZERO; arg = 0; return; }
-            if (t1 == t0 + 1 && memcmp(&lcf[t0], &one, sizeof(sc)) == 0) { kind = WK_VAR; arg = as_row(lv[t0]); }
+            if (t1 == t0 + 1 && memcmp(&lcf[t0], &one, sizeof(sc)) == 0 && !(flc.any && lscale[t0])) { kind = WK_VAR; arg = as_row(lv[t0]); }
         };
         // Poseidon annotations: validate, then route the S-box multipliers to the jointly evaluated values.
         // Anything unexpected leaves the plain program in place (it is complete on its own).
@@ -426,8 +522,13 @@ int bpr1cs_circuit_create(const bpr1cs_circuit_desc* d, bpr1cs_circuit** out) {
         for (auto& var : lv) var = as_row(var);   // (after the last check of the caller's own numbering)
         upload(c->lc_var, lv, s);
         upload(c->lc_coeff, lcf, s);
+        if (flc.any) {   // K_witness_scaled: beside lc_var, 1 + the value row of the public factor
+            std::vector<uint32_t> ls(nt);
+            for (uint32_t t = 0; t < nt; t++) ls[t] = lscale[t] ? d->m + lscale[t] : 0u;
+            upload(c->lc_scale, ls, s);
+        }
     }
-    if (cacheable) circuit_cache_insert(c, d, cache_key);
+    if (cacheable) circuit_cache_insert(c, d0, cache_key);
     *out = c;
     return BPR1CS_OK;
     }

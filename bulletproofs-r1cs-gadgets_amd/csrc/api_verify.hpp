@@ -65,7 +65,14 @@ static void verify_front(VerifyCtx& v, const bpr1cs_gens* g, const bpr1cs_circui
     launch_pow_tables(K_pow_tables{v.chal.p, v.plo.p, v.phi.p, B, v.H}, B, st);
     const uint32_t nslots = 3 * n + m + p + 1;
     v.wvec.alloc((size_t)nslots * B);
-    run_flatten(c, nslots, v.plo.p, v.phi.p, v.wvec.p, B, v.H, st);
+    // public coefficients (BPR1CS_VAR_SCALE): the flattening multiplies by the public inputs, which lie here as the caller's canonical
+    // bytes, proof-major - converted once (a non-canonical one reads as 0; K_verify_public below marks its proof malformed)
+    DevBuf<sc> pub_m;
+    if (c->n_sc_chunks) {
+        pub_m.alloc((size_t)p * B);
+        launch((uint64_t)p * B, K_public_mont{v.d_pub, pub_m.p, B, p}, st);
+    }
+    run_flatten(c, nslots, v.plo.p, v.phi.p, v.wvec.p, B, v.H, st, pub_m.p);
     v.gh.alloc((size_t)2 * N * B); v.dpart.alloc((size_t)N * B); v.delta.alloc(B); v.bsc.alloc((size_t)2 * B);
     launch((uint64_t)N * B, K_verify_gh{v.wvec.p, v.plo.p, v.phi.p, v.chal.p, v.uk.p, v.gh.p, v.gh.p + (size_t)N * B, v.dpart.p, B, v.H, n, N, lgN}, st);
     if (N >= 1024) {  // delta = sum_i y^-i wR_i wL_i in two levels (one thread per proof walking N values alone takes ~12 ms)

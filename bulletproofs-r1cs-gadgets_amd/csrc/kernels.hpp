@@ -639,6 +639,7 @@ struct K_poseidon_batch {  // gid = h ; in/out [count][width] Montgomery.  Inver
     }
 };
 
+template <class P> HD inline void witness_run(const P& p, uint32_t b);
 struct K_witness {  // thread per proof (sequential program)
     const WOp* ops;
     const uint32_t* lc_off;
@@ -671,51 +672,70 @@ struct K_witness {  // thread per proof (sequential program)
         uint32_t idx = 0xffffffffu;
         sc x;
     };
-    HD sc operand(uint32_t kind, uint32_t arg, uint32_t b, LcBits& lcb) const {
-        if (kind == WK_VAR) return value(arg, b);
-        if (kind == WK_ZERO) return sc_zero();
-        if (kind == WK_PX) return scratch(b).at(PX_A, arg);
-        if (kind == WK_PXINV) return scratch(b).at(PX_INVA, arg);
-        if (kind == WK_LC) {
-            sc acc = sc_zero();
-            for (uint32_t t = lc_off[arg]; t < lc_off[arg + 1]; t++) acc = sc_add(acc, sc_mul(lc_coeff[t], value(lc_var[t], b)));
-            return acc;
+    // one term of a combination (K_witness_scaled, below, has the form with a public coefficient)
+    HD sc term(uint32_t t, uint32_t b) const { return sc_mul(lc_coeff[t], value(lc_var[t], b)); }
+    HD void operator()(uint32_t b) const { witness_run(*this, b); }
+};
+// The sequential program (operands: witness_operand) over P = K_witness or K_witness_scaled: the two differ in P::term alone.
+template <class P>
+HD inline sc witness_operand(const P& p, uint32_t kind, uint32_t arg, uint32_t b, K_witness::LcBits& lcb) {
+    if (kind == WK_VAR) return p.value(arg, b);
+    if (kind == WK_ZERO) return sc_zero();
+    if (kind == WK_PX) return p.scratch(b).at(PX_A, arg);
+    if (kind == WK_PXINV) return p.scratch(b).at(PX_INVA, arg);
+    if (kind == WK_LC) {
+        sc acc = sc_zero();
+        for (uint32_t t = p.lc_off[arg]; t < p.lc_off[arg + 1]; t++) acc = sc_add(acc, p.term(t, b));
+        return acc;
+    }
+    const uint32_t k = arg & 0xffu;
+    if (kind == WK_LCBIT || kind == WK_LCNOTBIT) {
+        if (lcb.idx != (arg >> 8)) {
+            lcb.x = sc_from_mont(witness_operand(p, WK_LC, arg >> 8, b, lcb));   // 0 <= x < l < 2^253: bits 253..255 read 0
+            lcb.idx = arg >> 8;
         }
-        const uint32_t k = arg & 0xffu;
-        if (kind == WK_LCBIT || kind == WK_LCNOTBIT) {
-            if (lcb.idx != (arg >> 8)) {
-                lcb.x = sc_from_mont(operand(WK_LC, arg >> 8, b, lcb));   // 0 <= x < l < 2^253: bits 253..255 read 0
-                lcb.idx = arg >> 8;
-            }
-            uint32_t bit = (lcb.x.v[k >> 5] >> (k & 31)) & 1u;
-            if (kind == WK_LCNOTBIT) bit ^= 1u;
-            return bit ? sc_one_mont() : sc_zero();
-        }
-        sc raw = v_raw[(size_t)(arg >> 8) * B + b];
-        uint32_t bit = (raw.v[k >> 5] >> (k & 31)) & 1u;
-        if (kind == WK_NOTBIT) bit ^= 1u;
+        uint32_t bit = (lcb.x.v[k >> 5] >> (k & 31)) & 1u;
+        if (kind == WK_LCNOTBIT) bit ^= 1u;
         return bit ? sc_one_mont() : sc_zero();
     }
-    HD void operator()(uint32_t b) const {
-        uint32_t pi = 0;
-        LcBits lcb;
-        for (uint32_t i = 0; i < n; i++) {
-            if (pi < n_perms && perms[pi].first_mul == i) {
-                const PoseidonPerm& pm = perms[pi++];
-                const PoseidonTab& t = ptab[pm.table];
-                sc sh[PS_SIZE];
-                for (uint32_t k = 0; k < t.width; k++) sh[PS_N + k] = operand(WK_LC, pm.in_lc[k], b, lcb);
-                poseidon_team(t, pconst, scratch(b), sh, 8, 0, pm.first_mul, pm.covers);
-                if (pm.covers) { i += pm.covers - 1; continue; }
-            }
-            WOp op = ops[i];
-            sc l = operand(op.lkind, op.larg, b, lcb);
-            W[((size_t)0 * n + i) * B + b] = l;
-            sc r = (op.rkind == WK_INV_LEFT) ? sc_invert(l) : operand(op.rkind, op.rarg, b, lcb);
-            W[((size_t)1 * n + i) * B + b] = r;
-            W[((size_t)2 * n + i) * B + b] = sc_mul(l, r);
+    sc raw = p.v_raw[(size_t)(arg >> 8) * p.B + b];
+    uint32_t bit = (raw.v[k >> 5] >> (k & 31)) & 1u;
+    if (kind == WK_NOTBIT) bit ^= 1u;
+    return bit ? sc_one_mont() : sc_zero();
+}
+template <class P>
+HD inline void witness_run(const P& p, uint32_t b) {
+    uint32_t pi = 0;
+    K_witness::LcBits lcb;
+    const uint32_t n = p.n, B = p.B;
+    for (uint32_t i = 0; i < n; i++) {
+        if (pi < p.n_perms && p.perms[pi].first_mul == i) {
+            const PoseidonPerm& pm = p.perms[pi++];
+            const PoseidonTab& t = p.ptab[pm.table];
+            sc sh[PS_SIZE];
+            for (uint32_t k = 0; k < t.width; k++) sh[PS_N + k] = witness_operand(p, WK_LC, pm.in_lc[k], b, lcb);
+            poseidon_team(t, p.pconst, p.scratch(b), sh, 8, 0, pm.first_mul, pm.covers);
+            if (pm.covers) { i += pm.covers - 1; continue; }
         }
+        WOp op = p.ops[i];
+        sc l = witness_operand(p, op.lkind, op.larg, b, lcb);
+        p.W[((size_t)0 * n + i) * B + b] = l;
+        sc r = (op.rkind == WK_INV_LEFT) ? sc_invert(l) : witness_operand(p, op.rkind, op.rarg, b, lcb);
+        p.W[((size_t)1 * n + i) * B + b] = r;
+        p.W[((size_t)2 * n + i) * B + b] = sc_mul(l, r);
     }
+}
+// Public coefficients (BPR1CS_VAR_SCALE): the program of a circuit whose combinations hold scaled terms.  lc_scale runs beside lc_var:
+// 0 for a plain term, 1 + r for a term whose coefficient is multiplied by value row r of v_m (r = m + k: public input k of the proof
+// at hand).  A circuit without such a term never builds one of these: its program is K_witness as it was.
+struct K_witness_scaled : K_witness {
+    const uint32_t* lc_scale = nullptr;
+    HD sc term(uint32_t t, uint32_t b) const {
+        const sc x = sc_mul(lc_coeff[t], value(lc_var[t], b));
+        const uint32_t sw = lc_scale[t];
+        return sw ? sc_mul(x, v_m[(size_t)(sw - 1) * B + b]) : x;
+    }
+    HD void operator()(uint32_t b) const { witness_run(*this, b); }
 };
 struct K_load_wires {  // host-synthesised a_L a_R a_O (canonical) -> Montgomery
     const sc* raw;
@@ -912,6 +932,59 @@ struct K_flatten {  // gid = s*B + b
         wvec[g] = s >= n3 ? sc_neg(acc) : acc;
     }
 };
+// Public coefficients (BPR1CS_VAR_SCALE): entries whose coefficient is coeff x p_k[b], p_k public input k of proof b.
+// bpr1cs_circuit_create keeps them out of the lists above, in a second CSC over the slots that have any, so the two kernels above
+// read what they read without them; these two run behind K_flatten, and only for a circuit that has such entries.
+// Pass 1, gid = c*B + b -> part[c][b] = sum over the chunk of coeff * p_k[b] * z^(row+1)[b]: K_flatten_chunks' scheme (a block of 256
+// rows against the low table, one product with the high entry per block), one more product per entry for p_k.
+struct K_flatten_scaled_chunks {
+    const uint32_t* chunk_lo;  // [nchunks + 1] entry ranges (chunks of one slot are consecutive)
+    const uint32_t* ent_row;   // bit 31 / bit 30: the folded coefficient is +1 / -1
+    const uint32_t* ent_k;     // public input of the entry, < p
+    const sc* ent_coeff;       // Montgomery
+    const sc* pub_m;           // [p][B] Montgomery
+    const sc* plo;
+    const sc* phi;
+    sc* part;  // [nchunks][B]
+    uint32_t B, H;
+    HD void operator()(uint32_t g) const {
+        uint32_t c = g / B, b = g % B;
+        const sc* lo = plo + (size_t)2 * 256 * B;
+        const sc* hi = phi + (size_t)2 * H * B;
+        sc acc = sc_zero(), inner = sc_zero();
+        uint32_t cur = 0xffffffffu;
+        for (uint32_t t = chunk_lo[c]; t < chunk_lo[c + 1]; t++) {
+            const uint32_t rw = ent_row[t];   // the same for every proof of a wavefront: the branches below do not diverge
+            const uint32_t e = (rw & 0x3fffffffu) + 1, blk = e >> 8;
+            if (blk != cur) {
+                if (cur != 0xffffffffu) acc = sc_add(acc, sc_mul(inner, hi[(size_t)cur * B + b]));
+                inner = sc_zero();
+                cur = blk;
+            }
+            const sc zp = sc_mul(lo[(size_t)(e & 255u) * B + b], pub_m[(size_t)ent_k[t] * B + b]);
+            if (rw & 0x80000000u) inner = sc_add(inner, zp);
+            else if (rw & 0x40000000u) inner = sc_sub(inner, zp);
+            else inner = sc_add(inner, sc_mul(zp, ent_coeff[t]));
+        }
+        if (cur != 0xffffffffu) acc = sc_add(acc, sc_mul(inner, hi[(size_t)cur * B + b]));
+        part[g] = acc;
+    }
+};
+// Pass 2, gid = s*B + b: the chunk sums of scaled slot #s go into wvec[slot][b], which K_flatten wrote (subtracted for w_V, as there)
+struct K_flatten_scaled {
+    const uint32_t* slot;        // [nscaled] the slots that have scaled entries, ascending
+    const uint32_t* slot_chunk;  // [nscaled + 1] first chunk of each
+    const sc* part;
+    sc* wvec;
+    uint32_t B, n3;
+    HD void operator()(uint32_t g) const {
+        uint32_t s = g / B, b = g % B;
+        sc acc = sc_zero();
+        for (uint32_t c = slot_chunk[s]; c < slot_chunk[s + 1]; c++) acc = sc_add(acc, part[(size_t)c * B + b]);
+        const size_t w = (size_t)slot[s] * B + b;
+        wvec[w] = slot[s] >= n3 ? sc_sub(wvec[w], acc) : sc_add(wvec[w], acc);
+    }
+};
 
 // ------------------------------------------------------ witness check (BPR1CS_OPT_CHECK_WITNESS)
 // Is the assignment a job is about to prove a solution of its circuit?  a_L[i] a_R[i] = a_O[i] for every multiplier, and
@@ -973,6 +1046,9 @@ struct K_check_rows {
     const sc* v_m;              // [m][B]
     uint32_t* res;
     uint32_t B, Bpad, n3, m, c0;
+    // public coefficients (BPR1CS_VAR_SCALE): null for a circuit without any; else beside row_slot, 0 = a plain entry, 1 + r = the entry's
+    // value is multiplied by value row r of v_m (public input r - (committed values) of the proof at hand)
+    const uint32_t* row_scale = nullptr;
     HD void operator()(uint32_t g) const {
         const uint32_t c = c0 + g / Bpad, b = g % Bpad;
         if (b >= B) return;
@@ -981,7 +1057,11 @@ struct K_check_rows {
             sc acc = sc_zero();
             for (uint32_t t = row_off[j]; t < row_off[j + 1]; t++) {
                 const uint32_t sw = row_slot[t], slot = sw & 0x3fffffffu;   // the same for every proof of a wavefront: no divergence below
-                const sc x = slot < n3 ? W[(size_t)slot * B + b] : (slot < n3 + m ? v_m[(size_t)(slot - n3) * B + b] : sc_one_mont());
+                sc x = slot < n3 ? W[(size_t)slot * B + b] : (slot < n3 + m ? v_m[(size_t)(slot - n3) * B + b] : sc_one_mont());
+                if (row_scale) {
+                    const uint32_t sc_row = row_scale[t];
+                    if (sc_row) x = sc_mul(x, v_m[(size_t)(sc_row - 1) * B + b]);
+                }
                 if (sw & 0x80000000u) acc = sc_add(acc, x);
                 else if (sw & 0x40000000u) acc = sc_sub(acc, x);
                 else acc = sc_add(acc, sc_mul(x, row_coeff[t]));
@@ -1885,6 +1965,18 @@ struct K_verify_public {  // gid = b
         for (uint32_t k = 0; k < p; k++) acc = sc_add(acc, public_term(wpub, pub, B, p, b, k, bad));
         if (bad) fail[b] = 1;
         else wc[b] = sc_add(wc[b], acc);
+    }
+};
+// the verifier's public inputs, canonical bytes [B][p][32] -> Montgomery, element-major [p][B], for K_flatten_scaled_chunks.  A
+// non-canonical input reads as 0: its proof is marked malformed by K_verify_public whatever its weights come to.
+struct K_public_mont {  // gid = k*B + b
+    const uint8_t* pub;
+    sc* out;
+    uint32_t B, p;
+    HD void operator()(uint32_t g) const {
+        const uint32_t k = g / B, b = g % B;
+        const uint8_t* v = pub + ((size_t)b * p + k) * 32;
+        out[g] = scalar_bytes_canonical(v) ? sc_to_mont(sc_load_raw(v)) : sc_zero();
     }
 };
 // the proof's own points: decompress, multiply by their mega-check scalar

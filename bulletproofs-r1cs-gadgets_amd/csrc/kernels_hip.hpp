@@ -44,12 +44,13 @@ struct WireCache {
     sc l[2], r[2], o[2];
 };
 // the team's value of linear combination #j: the terms spread over the lanes, every lane ends with the sum
-template <int T>
-__device__ inline sc team_lc(const K_witness& p, uint32_t j, uint32_t b, uint32_t lane, bool& fenced) {
+// (P = K_witness, or K_witness_scaled for a circuit with public coefficients: P::term is the one difference)
+template <int T, class P>
+__device__ inline sc team_lc(const P& p, uint32_t j, uint32_t b, uint32_t lane, bool& fenced) {
     if (!fenced) { __threadfence_block(); fenced = true; }  // earlier wires are read back from memory
     sc acc = sc_zero();
     uint32_t t1 = p.lc_off[j + 1];
-    for (uint32_t t = p.lc_off[j] + lane; t < t1; t += T) acc = sc_add(acc, sc_mul(p.lc_coeff[t], p.value(p.lc_var[t], b)));
+    for (uint32_t t = p.lc_off[j] + lane; t < t1; t += T) acc = sc_add(acc, p.term(t, b));
     return team_sum<T>(acc);
 }
 // WK_LCBIT / WK_LCNOTBIT: the canonical value of the combination named last stays in LDS, in the team's own slot behind its Poseidon
@@ -57,12 +58,12 @@ __device__ inline sc team_lc(const K_witness& p, uint32_t j, uint32_t b, uint32_
 // address - and reads back only after its own store, so no barrier is needed.  Between operands the cache costs k_witness_team no
 // vector register: the slot hangs off the `sh` pointer the kernel holds anyway, `idx` is wave-uniform (the program is the same for
 // every proof), and taking a bit is one LDS read.
-template <int T>
-__device__ inline void team_lcbits_fill(const K_witness& p, uint32_t j, uint32_t b, uint32_t lane, bool& fenced, sc* slot) {
+template <int T, class P>
+__device__ inline void team_lcbits_fill(const P& p, uint32_t j, uint32_t b, uint32_t lane, bool& fenced, sc* slot) {
     *slot = sc_from_mont(team_lc<T>(p, j, b, lane, fenced));   // 0 <= x < l < 2^253: bits 253..255 read 0
 }
-template <int T>
-__device__ inline sc team_operand(const K_witness& p, uint32_t kind, uint32_t arg, uint32_t b, uint32_t lane, const WireCache& wc, bool& fenced, uint32_t& lcb_idx, sc* lcb) {
+template <int T, class P>
+__device__ inline sc team_operand(const P& p, uint32_t kind, uint32_t arg, uint32_t b, uint32_t lane, const WireCache& wc, bool& fenced, uint32_t& lcb_idx, sc* lcb) {
     if (kind == WK_ZERO) return sc_zero();
     if (kind == WK_PX) return p.scratch(b).at(PX_A, arg);      // written (and fenced) by poseidon_team
     if (kind == WK_PXINV) return p.scratch(b).at(PX_INVA, arg);
@@ -93,8 +94,8 @@ __device__ inline sc team_operand(const K_witness& p, uint32_t kind, uint32_t ar
     if (kind == WK_NOTBIT) bit ^= 1u;
     return bit ? sc_one_mont() : sc_zero();
 }
-template <int T>
-__global__ void __launch_bounds__(64) k_witness_team(K_witness p) {
+template <int T, class P>
+__device__ __forceinline__ void witness_team_run(const P& p) {
     if (p.prio == 1) __builtin_amdgcn_s_setprio(1); else if (p.prio == 2) __builtin_amdgcn_s_setprio(2); else if (p.prio == 3) __builtin_amdgcn_s_setprio(3);
     const uint32_t lane = threadIdx.x & (T - 1);
     uint32_t b = (blockIdx.x * 64u + threadIdx.x) / T;
@@ -138,6 +139,11 @@ __global__ void __launch_bounds__(64) k_witness_team(K_witness p) {
         wc.idx[0] = i; wc.l[0] = l; wc.r[0] = r; wc.o[0] = o;
     }
 }
+template <int T>
+__global__ void __launch_bounds__(64) k_witness_team(K_witness p) { witness_team_run<T>(p); }
+// the program of a circuit with public coefficients in its combinations (BPR1CS_VAR_SCALE): launched for such circuits only
+template <int T>
+__global__ void __launch_bounds__(64) k_witness_team_scaled(K_witness_scaled p) { witness_team_run<T>(p); }
 
 // Inverse-S-box permutations in bulk: 8 lanes per permutation, 8 permutations per wavefront
 __global__ void __launch_bounds__(64) k_poseidon_team(K_poseidon_batch p, uint32_t count) {

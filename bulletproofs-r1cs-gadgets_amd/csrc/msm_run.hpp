@@ -344,13 +344,22 @@ static void run_msm(const bpr1cs_gens* g, MsmSeg s0, MsmSeg s1, uint32_t B, DevB
 }
 
 // constraint columns weighted by powers of z: wvec[slot][b] (first `nslots` slots of the circuit)
+// pub_m: the proofs' public inputs in Montgomery form, element-major [p][B] - read only when the circuit has public coefficients
+// (BPR1CS_VAR_SCALE): their pass runs behind K_flatten and takes its chunk sums' room over (flatten_part_chunks: the larger of the two)
+static uint32_t flatten_part_chunks(const bpr1cs_circuit* c, uint32_t nslots) {
+    return std::max(c->h_slot_chunk.empty() ? 0u : c->h_slot_chunk[nslots], c->n_sc_chunks);
+}
 static void run_flatten(const bpr1cs_circuit* c, uint32_t nslots, const sc* plo, const sc* phi, sc* wvec, uint32_t B, uint32_t H, dev_stream_t st,
-                        sc* part_buf = nullptr /* optional room for the chunk sums: h_slot_chunk[nslots] * B scalars */) {
+                        const sc* pub_m, sc* part_buf = nullptr /* optional room for the chunk sums: flatten_part_chunks(c, nslots) * B scalars */) {
     uint32_t nch = c->h_slot_chunk[nslots];
     DevBuf<sc> part;
-    if (!part_buf) { part.alloc((size_t)(nch ? nch : 1) * B); part_buf = part.p; }
+    if (!part_buf) { const uint32_t room = flatten_part_chunks(c, nslots); part.alloc((size_t)(room ? room : 1) * B); part_buf = part.p; }
     launch((uint64_t)nch * B, K_flatten_chunks{c->chunk_lo.p, c->ent_row.p, c->ent_coeff.p, plo, phi, part_buf, B, H}, st);
     launch((uint64_t)nslots * B, K_flatten{c->slot_chunk.p, part_buf, wvec, B, 3 * c->n}, st);
+    if (!c->n_sc_chunks) return;
+    if (!pub_m) throw DevError{BPR1CS_ERR_INVALID_ARGUMENT};   // (every caller of a circuit with p > 0 has the block)
+    launch((uint64_t)c->n_sc_chunks * B, K_flatten_scaled_chunks{c->sc_chunk_lo.p, c->sc_ent_row.p, c->sc_ent_k.p, c->sc_ent_coeff.p, pub_m, plo, phi, part_buf, B, H}, st);
+    launch((uint64_t)c->n_sc_slots * B, K_flatten_scaled{c->sc_slot.p, c->sc_slot_chunk.p, part_buf, wvec, B, 3 * c->n}, st);
 }
 
 #if defined(BPR1CS_HOSTSIM)

@@ -169,6 +169,11 @@ bpr1cs_circuit* CircuitCompiler::finish(uint32_t* n_out, uint32_t* q_out, uint32
             LinearCombination lc = lc0.simplify();
             for (auto& t : lc.terms) {
                 if (t.second.is_zero()) continue;
+                if (t.first.pub) {   // a public coefficient: the marker (coefficient 1), then the term
+                    lc_var.push_back((BPR1CS_VAR_SCALE << 28) | (t.first.pub - 1));
+                    auto one = Scalar::one().to_bytes();
+                    lc_coeff.insert(lc_coeff.end(), one.begin(), one.end());
+                }
                 lc_var.push_back(t.first.encode());
                 auto b = t.second.to_bytes();
                 lc_coeff.insert(lc_coeff.end(), b.begin(), b.end());
@@ -184,7 +189,7 @@ bpr1cs_circuit* CircuitCompiler::finish(uint32_t* n_out, uint32_t* q_out, uint32
         auto same_terms = [](const LinearCombination& a, const LinearCombination& b) {
             if (a.terms.size() != b.terms.size()) return false;
             for (size_t i = 0; i < a.terms.size(); i++)
-                if (a.terms[i].first.encode() != b.terms[i].first.encode() || !(a.terms[i].second == b.terms[i].second)) return false;
+                if (!(a.terms[i].first == b.terms[i].first) || !(a.terms[i].second == b.terms[i].second)) return false;
             return true;
         };
         auto add_bits_lc = [&](const WitnessHint& h) {
@@ -322,6 +327,50 @@ static size_t run_gadget(const GadgetSpec& g, Harness& h) {
         positive_no_gadget_lc(h.cs, a, va, bits);
         positive_no_gadget_lc(h.cs, b, vb, bits);
         return 1;
+    }
+    if (g.name == "set_membership_lean") {  // one-of-k set membership with the items as COEFFICIENTS of the bits: sum item_i x bit_i = value in one
+        // row, no multiplier per item (n = k against the 3k of vector_product_gadget).  ip = [k]; sp = [item_0 .. item_k-1] bakes the set (the only
+        // form Prover and Verifier support); COMPILED without sp the items are public inputs 0 .. k-1, used as public coefficients
+        const size_t k = g.ip.at(0);
+        const bool items_public = g.sp.empty() && dynamic_cast<CircuitCompiler*>(&h.cs) != nullptr;
+        if (!items_public && g.sp.size() < k) throw R1CSError::GadgetError("set_membership_lean: sp = the k items");
+        std::vector<AllocatedQuantity> bit_vars;
+        for (size_t i = 0; i < k; i++) {
+            auto q = AQ(i);
+            bit_gadget(h.cs, q);
+            bit_vars.push_back(q);
+        }
+        vector_sum_gadget(h.cs, bit_vars, 1);
+        auto val = AQ(k);
+        std::vector<Term> row{{val.variable, -Scalar::one()}};
+        for (size_t i = 0; i < k; i++) {
+            if (items_public) row.push_back({bit_vars[i].variable.times_public((uint32_t)i), Scalar::one()});
+            else row.push_back({bit_vars[i].variable, g.sp[i]});
+        }
+        h.cs.constrain(LinearCombination(row));
+        return k + 1;
+    }
+    if (g.name == "weighted_sum_bound") {  // 0 <= budget - sum w_i x_i < 2^bits: the bits of ONE combination (BPR1CS_W_LCBIT), n = bits whatever k is.
+        // ip = [k, bits]; sp = [w_0 .. w_k-1, budget] bakes them; COMPILED without sp the weights are public coefficients 0 .. k-1 and the
+        // budget is public input k
+        const size_t k = g.ip.at(0), bits = g.ip.at(1);
+        if (bits > 252) throw R1CSError::GadgetError("weighted_sum_bound: at most 252 bits");
+        const bool weights_public = g.sp.empty() && dynamic_cast<CircuitCompiler*>(&h.cs) != nullptr;
+        if (!weights_public && g.sp.size() < k + 1) throw R1CSError::GadgetError("weighted_sum_bound: sp = the k weights and the budget");
+        std::vector<Term> terms;
+        if (weights_public) terms.push_back({Variable::Public((uint32_t)k), Scalar::one()});
+        else terms.push_back({Variable::One(), g.sp[k]});
+        std::optional<Scalar> slack;
+        if (!weights_public && (k == 0 || h.value(0))) slack = g.sp[k];
+        for (size_t i = 0; i < k; i++) {
+            const Variable x = h.commit(i);
+            if (weights_public) terms.push_back({x.times_public((uint32_t)i), -Scalar::one()});
+            else terms.push_back({x, -g.sp[i]});
+            if (slack) slack = *slack - g.sp[i] * *h.value(i);
+        }
+        const LinearCombination lc(terms);
+        positive_no_gadget_lc(h.cs, lc, slack, bits);
+        return k;
     }
     if (g.name == "set_membership") {  // src/gadget_set_membership.rs:93-134 ; ip = [k, items(lo,hi)...]
         size_t k = g.ip.at(0);

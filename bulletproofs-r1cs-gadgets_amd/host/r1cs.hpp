@@ -101,6 +101,16 @@ struct LinearCombination;
 struct Variable {
     VarKind kind;
     uint32_t index;
+    // public coefficient (BPR1CS_VAR_SCALE, include/bpr1cs.h "Public coefficients"): 0 = none, 1 + k = the term's coefficient is
+    // multiplied by public input k of the proof at hand.  Like Public, understood by CircuitCompiler only.
+    uint32_t pub = 0;
+    Variable times_public(uint32_t k) const {
+        if (kind == VarKind::One || kind == VarKind::Public || pub) throw_not_scalable();
+        Variable v = *this;
+        v.pub = 1 + k;
+        return v;
+    }
+    static void throw_not_scalable();   // (R1CSError is declared above; defined below the struct to keep this one an aggregate)
     static Variable Committed(uint32_t i) { return {VarKind::Committed, i}; }
     static Variable MultiplierLeft(uint32_t i) { return {VarKind::MultiplierLeft, i}; }
     static Variable MultiplierRight(uint32_t i) { return {VarKind::MultiplierRight, i}; }
@@ -108,8 +118,11 @@ struct Variable {
     static Variable One() { return {VarKind::One, 0}; }
     static Variable Public(uint32_t k) { return {VarKind::Public, k}; }
     uint32_t encode() const { return ((uint32_t)kind << 28) | index; }
-    bool operator==(const Variable& o) const { return kind == o.kind && index == o.index; }
+    bool operator==(const Variable& o) const { return kind == o.kind && index == o.index && pub == o.pub; }
 };
+inline void Variable::throw_not_scalable() {
+    throw R1CSError::GadgetError("times_public: a public coefficient scales a committed value or a wire, once (a public input times One is Variable::Public)");
+}
 
 // The terms of a linear combination: a vector with room for two terms inside the object.  Most combinations a gadget builds have one
 // or two (a variable; x - y; a wire minus a constant): with std::vector every one of them was a heap block - 1.16 million allocations,
@@ -231,7 +244,7 @@ struct LinearCombination {
         r.terms.reserve(terms.size());
         for (auto& t : terms) {
             const uint32_t code = t.first.encode();
-            size_t h = (code * 0x9e3779b1u) & mask;
+            size_t h = ((code ^ (t.first.pub * 0x85ebca6bu)) * 0x9e3779b1u) & mask;   // (like terms merge only when the public factor is equal)
             for (;;) {
                 const uint64_t e = table[h];
                 if ((uint32_t)(e >> 32) != stamp) {
@@ -240,7 +253,7 @@ struct LinearCombination {
                     break;
                 }
                 auto& have = r.terms[(uint32_t)e];
-                if (have.first.encode() == code) { have.second += t.second; break; }
+                if (have.first == t.first) { have.second += t.second; break; }
                 h = (h + 1) & mask;
             }
         }
@@ -534,7 +547,8 @@ public:
     // would make the library read a tail block that is not behind `values` / `commitments`
     void export_csr(std::vector<uint32_t>& row_off, std::vector<uint32_t>& tvar, std::vector<uint8_t>& tcoeff, bool allow_public = false) const {
         size_t nnz = 0;
-        for (auto& lc : constraints) nnz += lc.terms.size();
+        for (auto& lc : constraints)
+            for (auto& t : lc.terms) nnz += t.first.pub ? 2 : 1;   // (a public coefficient: marker + term)
         row_off.assign(1, 0);
         row_off.reserve(constraints.size() + 1);
         tvar.resize(nnz);
@@ -545,6 +559,14 @@ public:
                 if (t.first.kind == VarKind::Public && !allow_public)
                     throw R1CSError::GadgetError("Variable::Public in a Prover / Verifier: only CircuitCompiler understands public inputs");
                 if (t.first.kind == VarKind::Public && t.second.is_zero()) continue;   // (bpr1cs_circuit_create refuses a public term that says nothing)
+                if (t.first.pub) {
+                    if (!allow_public)
+                        throw R1CSError::GadgetError("a public coefficient in a Prover / Verifier: only CircuitCompiler understands public inputs");
+                    if (t.second.is_zero()) continue;   // (as above: a scaled term whose coefficient came out 0 is dropped)
+                    tvar[k] = (BPR1CS_VAR_SCALE << 28) | (t.first.pub - 1);
+                    Scalar::one().write_bytes(&tcoeff[32 * k]);
+                    k++;
+                }
                 tvar[k] = t.first.encode();
                 t.second.write_bytes(&tcoeff[32 * k]);
                 k++;
@@ -620,6 +642,7 @@ public:
         Scalar acc;
         for (auto& t : lc.terms) {
             Scalar val;
+            if (t.first.pub) throw R1CSError::GadgetError("a public coefficient in a Prover: only CircuitCompiler understands public inputs");
             switch (t.first.kind) {
                 case VarKind::Committed: val = v_[t.first.index]; break;
                 case VarKind::MultiplierLeft: val = a_L[t.first.index]; break;

@@ -84,6 +84,9 @@ typedef struct bpr1cs_circuit bpr1cs_circuit; /* the constraint system a Prover 
 #define BPR1CS_VAR_MUL_OUT 3u   /* Variable::MultiplierOutput(i) */
 #define BPR1CS_VAR_ONE 4u       /* Variable::One()               */
 #define BPR1CS_VAR_PUBLIC 5u    /* public input k of THIS proof: a scalar the verifier knows (see "Public inputs" below) */
+#define BPR1CS_VAR_SCALE 8u     /* not a term of its own: multiplies the coefficient of the term that FOLLOWS it in the same row /
+                                   combination by (its own coefficient) x p_k, p_k = public input k of the proof at hand (see "Public
+                                   coefficients" below).  (8 is free: the variable kinds pinned as refused are 6, 7, 9 and 10.) */
 
 /* Public inputs.  A constant of the statement that differs from proof to proof - the root of the reference's tree gadgets
  * (`constrain(prev_hash - root)`, src/gadget_vsmt_4.rs, src/gadget_vsmt_2.rs), a bound - need not be baked into the coefficient of
@@ -94,7 +97,7 @@ typedef struct bpr1cs_circuit bpr1cs_circuit; /* the constraint system a Prover 
  * description by the same rule, and the library - which cannot see how long the caller's arrays are - reads exactly batch x p x 32
  * bytes behind the committed values / points.  A public input enters LINEARLY with a constant coefficient, like One;
  * BPR1CS_W_BIT / BPR1CS_W_NOTBIT of one are BPR1CS_ERR_INVALID_ARGUMENT.  A public COEFFICIENT of a wire (the set_i x bit_i of
- * gadget_set_membership.rs) is a different feature and is not provided.
+ * gadget_set_membership.rs) is written with BPR1CS_VAR_SCALE ("Public coefficients" below).
  * The values ride in arrays the calls already take, as a tail block:
  *   prove calls   `values`      = batch x m x 32 committed values, then batch x p x 32 public inputs, proof-major
  *                 (v_blindings, commitments_out, transcripts: over the m committed values only, as before)
@@ -104,6 +107,23 @@ typedef struct bpr1cs_circuit bpr1cs_circuit; /* the constraint system a Prover 
  * Merlin transcript - upstream absorbs no constants either -, so a proof is byte for byte the proof of the circuit that has
  * coeff x p_k folded into its One coefficients, and a verifier running that baked circuit accepts it.  The cross-proof weights DO
  * bind them (bpr1cs_verify_batch_combined). */
+
+/* Public coefficients.  A marker (BPR1CS_VAR_SCALE << 28 | k, s) followed, in the same row of `term_var` or the same combination of
+ * `lc_var`, by a term (var, c) stands for the SINGLE term s c p_k x var: the coefficient of a wire or of a committed value differs
+ * from proof to proof (a set whose items are per-proof data, a weighted sum with per-proof weights) without a multiplier per
+ * coefficient.  `var` is of kind COMMITTED, MUL_LEFT, MUL_RIGHT or MUL_OUT, and every check of an unmarked term applies to it
+ * unchanged (a combination reads wires of EARLIER multipliers only, a committed index is < m).  BPR1CS_ERR_INVALID_ARGUMENT: a marker
+ * that is the last term of its row or combination; a marker followed by One, a public term or another marker; k >= 2^20; s or c
+ * that is non-canonical or 0 (mod l) - as for public terms, only a term that uses its input may size p.  Combinations named by
+ * BPR1CS_W_LC, BPR1CS_W_LCBIT / BPR1CS_W_LCNOTBIT and Poseidon annotations may all hold marked terms.
+ * NOT provided: a public input times One - that is BPR1CS_VAR_PUBLIC, which stays the only way to write it - and products of two
+ * public inputs.
+ * p = 1 + the highest index over public terms AND markers, in rows and combinations.  The values ride where they ride today - the
+ * tail block of `values` and of `commitments` - and no call signature changes.  A description without a marker is byte for byte
+ * what it was, creates the same circuit object and launches the same kernels.
+ * Public inputs stay out of the Merlin transcript, so a proof is byte for byte the proof of the circuit with s c p_k baked in as a
+ * constant coefficient, and a verifier running that baked circuit accepts it.  The cross-proof weights already absorb all p public
+ * inputs of a proof (bpr1cs_verify_batch_combined), whichever way the circuit uses them: nothing changes there. */
 
 /* Witness-program operand kinds (device-side constraint synthesis). */
 #define BPR1CS_W_LC 0u       /* value of linear combination #arg (cs.multiply / evaluate_lc)   */

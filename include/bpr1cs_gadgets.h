@@ -32,6 +32,13 @@
  *                      prove and synthesize entry points below take `values`, `v_blindings` and `m` of the PLAIN gadget (blindings of
  *                      uncommitted entries are ignored); `commitments_out` holds the committed ones only, in gadget order, packed per
  *                      proof; bpr1cs_gadget_compile reports the smaller m and the verify entry points take the smaller list.
+ *   "set_membership_lean" ip=[k] sp=[item_0 .. item_k-1]        values: k bits, value (m = k + 1)   one-of-k set membership in k multipliers
+ *                      (against 3k for "set_membership"): bit_gadget x k, vector_sum_gadget(.., 1), ONE row sum item_i x bit_i - value.
+ *                      sp bakes the set; COMPILED without sp the items are public inputs 0 .. k-1 of every proof, used as public
+ *                      coefficients of the bit wires (bpr1cs.h "Public coefficients"): one circuit, a different set per proof
+ *   "weighted_sum_bound" ip=[k, bits] sp=[w_0 .. w_k-1, budget]   values: x_0 .. x_k-1 (m = k)        0 <= budget - sum w_i x_i < 2^bits in `bits`
+ *                      multipliers whatever k is (positive_no_gadget_lc of the combination).  sp bakes weights and budget; COMPILED
+ *                      without sp the weights are public coefficients 0 .. k-1 and the budget is public input k
  * The statics (0 / 101 / 0...) are committed with blinding 0 (reference gadget_poseidon.rs:554-578).
  * `poseidon_blob` = bulletproofs-r1cs-gadgets_amd/data/poseidon_params_ristretto.bin (may be NULL for non-Poseidon gadgets).
  * Environment (diagnostics only): BPR1CS_DEBUG_FRONT - Prover::prove prints the milliseconds of its stages (circuit export, witness
