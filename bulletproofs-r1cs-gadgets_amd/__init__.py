@@ -121,6 +121,8 @@ def load_library(path=None):
     lib.bpr1cs_transcript_new.argtypes = [cp, sz]
     lib.bpr1cs_transcript_new.restype = vp
     lib.bpr1cs_transcript_free.argtypes = [vp]
+    lib.bpr1cs_transcript_clone.argtypes = [vp]
+    lib.bpr1cs_transcript_clone.restype = vp
     lib.bpr1cs_transcript_append_message.argtypes = [vp, cp, sz, cp, sz]
     lib.bpr1cs_transcript_challenge_bytes.argtypes = [vp, cp, sz, cp, sz]
     lib.bpr1cs_poseidon_permutation_batch.argtypes = [vp, ctypes.c_int, cp, sz, cp]
@@ -346,7 +348,24 @@ def refusal(proof_bytes):
     return dict(gate=first(REFUSAL_OFF_GATE), row=first(REFUSAL_OFF_ROW), gates=w(REFUSAL_OFF_GATE_COUNT), rows=w(REFUSAL_OFF_ROW_COUNT))
 
 
-def verify_batch(gens, circuit, label, proofs, commitments, batch, seeds=None, publics=None):
+LABEL_TRANSCRIPTS = 1 << (8 * ctypes.sizeof(ctypes.c_size_t) - 1)   # BPR1CS_LABEL_TRANSCRIPTS
+
+
+def _start(label, transcripts):
+    """Where a verifier call's transcripts start -> the (label, label_len) pair of the C ABI and what must outlive the call.
+    transcripts = None: Transcript::new(label).  Otherwise `label` is None and `transcripts` is one Transcript (every proof starts from
+    a copy; it is advanced only when the batch is that one proof) or a list of `batch` of them (proof i starts from transcripts[i],
+    which is left where upstream's `&mut transcript` is after verify(): include/bpr1cs.h, BPR1CS_LABEL_TRANSCRIPTS)."""
+    if transcripts is None:
+        return label, len(label), None
+    if label is not None:
+        raise ValueError("label and transcripts exclude each other: pass label=None with transcripts=")
+    ts = list(transcripts) if isinstance(transcripts, (list, tuple)) else [transcripts]
+    arr = (ctypes.c_void_p * max(1, len(ts)))(*[t.h if t is not None else None for t in ts])
+    return ctypes.cast(arr, ctypes.c_char_p), LABEL_TRANSCRIPTS | len(ts), arr
+
+
+def verify_batch(gens, circuit, label, proofs, commitments, batch, seeds=None, publics=None, transcripts=None):
     """proofs: list of bytes or concatenated bytes; commitments: list of lists (each m x 32 bytes) or bytes.
     -> list of bool (Verifier::verify accepted).  seeds: batch*32 bytes for the verifier's TranscriptRng
     (default: fresh os.urandom, as upstream's thread_rng)."""
@@ -358,11 +377,12 @@ def verify_batch(gens, circuit, label, proofs, commitments, batch, seeds=None, p
     cm = _tail(cm, publics, circuit, batch)   # public inputs of the proofs (bytes batch*p*32 or per-proof lists): behind the points
     assert len(pf) == batch * circuit.proof_len
     ok = (ctypes.c_int * batch)()
-    _chk(gens.lib.bpr1cs_verify_batch(gens.h, circuit.h, label, len(label), pf, cm or b"\0", seeds, batch, ok))
+    start, start_len, _keep = _start(label, transcripts)
+    _chk(gens.lib.bpr1cs_verify_batch(gens.h, circuit.h, start, start_len, pf, cm or b"\0", seeds, batch, ok))
     return [bool(x) for x in ok]
 
 
-def verify_batch_combined(gens, circuit, label, proofs, commitments, batch, batch_seed=None, index_base=0, seeds=None, publics=None):
+def verify_batch_combined(gens, circuit, label, proofs, commitments, batch, batch_seed=None, index_base=0, seeds=None, publics=None, transcripts=None):
     """Cross-proof batched mega-check of this caller's `batch` proofs -> (partial point: 32 bytes, wellformed: bool).
     The whole job is accepted iff points_sum_is_identity(all callers' points) and all callers were well-formed.
     batch_seed / seeds default to fresh os.urandom (the weights must not be predictable, see include/bpr1cs.h)."""
@@ -377,12 +397,13 @@ def verify_batch_combined(gens, circuit, label, proofs, commitments, batch, batc
     assert len(pf) == batch * circuit.proof_len and len(batch_seed) == 32
     out = ctypes.create_string_buffer(32)
     wf = ctypes.c_int()
-    _chk(gens.lib.bpr1cs_verify_batch_combined(gens.h, circuit.h, label, len(label), pf, cm or b"\0", seeds, batch_seed, index_base, batch,
+    start, start_len, _keep = _start(label, transcripts)
+    _chk(gens.lib.bpr1cs_verify_batch_combined(gens.h, circuit.h, start, start_len, pf, cm or b"\0", seeds, batch_seed, index_base, batch,
                                                out, ctypes.byref(wf)))
     return out.raw, bool(wf.value)
 
 
-def verify_batch_scalars(gens, circuit, label, proofs, commitments, batch, batch_seed=None, index_base=0, seeds=None, publics=None):
+def verify_batch_scalars(gens, circuit, label, proofs, commitments, batch, batch_seed=None, index_base=0, seeds=None, publics=None, transcripts=None):
     """First half of the multi-GPU batched verifier -> (combined scalar vector: (2N+2)*32 bytes in base order
     B, B~, G.., H.., own-points sum: 32 bytes, wellformed)."""
     if batch_seed is None:
@@ -396,7 +417,8 @@ def verify_batch_scalars(gens, circuit, label, proofs, commitments, batch, batch
     out = ctypes.create_string_buffer(32 * (2 * N + 2))
     own = ctypes.create_string_buffer(32)
     wf = ctypes.c_int()
-    _chk(gens.lib.bpr1cs_verify_batch_scalars(gens.h, circuit.h, label, len(label), pf, cm or b"\0", seeds, batch_seed, index_base, batch,
+    start, start_len, _keep = _start(label, transcripts)
+    _chk(gens.lib.bpr1cs_verify_batch_scalars(gens.h, circuit.h, start, start_len, pf, cm or b"\0", seeds, batch_seed, index_base, batch,
                                               out, own, ctypes.byref(wf)))
     return out.raw, own.raw, bool(wf.value)
 
@@ -431,7 +453,7 @@ class Comm:
             pass
 
 
-def verify_batch_sharded(gens, circuit, label, proofs, commitments, batch, comm=None, batch_seed=None, index_base=0, seeds=None, publics=None):
+def verify_batch_sharded(gens, circuit, label, proofs, commitments, batch, comm=None, batch_seed=None, index_base=0, seeds=None, publics=None, transcripts=None):
     """The multi-GPU batched verifier in one call per rank (bpr1cs_verify_batch_sharded: RCCL all_gathers inside the library)
     -> True / False, the same on every rank.  comm = None: a job of one rank."""
     if batch_seed is None:
@@ -442,7 +464,8 @@ def verify_batch_sharded(gens, circuit, label, proofs, commitments, batch, comm=
     cm = commitments if isinstance(commitments, (bytes, bytearray)) else b"".join(b"".join(c) for c in commitments)
     cm = _tail(cm, publics, circuit, batch)   # public inputs of the proofs (bytes batch*p*32 or per-proof lists): behind the points
     ok = ctypes.c_int()
-    _chk(gens.lib.bpr1cs_verify_batch_sharded(gens.h, circuit.h, label, len(label), pf, cm or b"\0", seeds, batch_seed, index_base, batch,
+    start, start_len, _keep = _start(label, transcripts)
+    _chk(gens.lib.bpr1cs_verify_batch_sharded(gens.h, circuit.h, start, start_len, pf, cm or b"\0", seeds, batch_seed, index_base, batch,
                                               comm.h if comm is not None else None, ctypes.byref(ok)))
     return bool(ok.value)
 
@@ -551,6 +574,15 @@ class Transcript:
         out = ctypes.create_string_buffer(n)
         self.lib.bpr1cs_transcript_challenge_bytes(self.h, label, len(label), out, n)
         return out.raw
+
+    def clone(self):
+        """an independent copy in the same state (upstream: Transcript::clone)"""
+        t = Transcript.__new__(Transcript)
+        t.lib = self.lib
+        t.h = self.lib.bpr1cs_transcript_clone(self.h)
+        if not t.h:
+            raise MemoryError("bpr1cs_transcript_clone")
+        return t
 
     def __del__(self):
         try:

@@ -153,8 +153,12 @@ extern "C" int bpr1cs_verify_batch_sharded(const bpr1cs_gens* g, const bpr1cs_ci
     std::vector<uint8_t> vec(vlen, 0), all;
     uint8_t own[32] = {0}, slice_pt[32] = {0};
     int wf = 0;
-    int rc_local = bpr1cs_verify_batch_scalars(g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch_seed, index_base, batch,
-                                               vec.data(), own, &wf);
+    //    (label, label_len) are parsed here and nowhere below: with BPR1CS_LABEL_TRANSCRIPTS they are the caller's transcripts, and a
+    //    refused list is a local failure like any other
+    VerifyHandles vh;
+    int rc_local = vh.parse(label, label_len, batch);
+    if (rc_local == BPR1CS_OK)
+        rc_local = verify_batch_scalars_parsed(g, c, vh.ts, proofs, commitments, verifier_rng_seeds, batch_seed, index_base, batch, vec.data(), own, &wf);
     if (rc_local != BPR1CS_OK) { std::fill(vec.begin(), vec.end(), 0); memset(own, 0, 32); wf = 0; }
     // 2. all_gather of the scalar vectors ((2N+2)*32 bytes per rank, ~2 MB at N = 32768), summed mod l
     //    A failure of the gather on THIS rank (allocation, HIP error) does not end the call either: the second collective below
@@ -180,6 +184,7 @@ extern "C" int bpr1cs_verify_batch_sharded(const bpr1cs_gens* g, const bpr1cs_ci
     rc = comm_all_gather(g, comm, gb2, mine, all);
     if (rc_local == BPR1CS_OK) rc_local = rc;
     if (rc_local != BPR1CS_OK) return rc_local;   // a local failure (out of memory, invalid argument ...) is an error, not a rejected proof
+    vh.finish(BPR1CS_OK);   // the call returns BPR1CS_OK from here on, whatever the verdict: the caller's transcripts follow their proofs
     std::vector<uint8_t> pts((size_t)2 * world * 32);
     bool all_wf = true;
     for (int r = 0; r < world; r++) {

@@ -928,7 +928,7 @@ extern "C" {
 int bpr1cs_prove_batch_begin(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,
                              const uint8_t* values, const uint8_t* v_blindings, const uint8_t* rng_seeds,
                              const uint8_t* wires, size_t batch, bpr1cs_job** job_out) {
-    if (!label) return BPR1CS_ERR_INVALID_ARGUMENT;
+    if (!label || (label_len & BPR1CS_LABEL_TRANSCRIPTS)) return BPR1CS_ERR_INVALID_ARGUMENT;   // (caller transcripts: bpr1cs_prove_batch_transcripts)
     const strobe s0 = label_state(label, label_len);
     return prove_job_begin(g, c, &s0, 1, false, values, v_blindings, rng_seeds, wires, batch, job_out);
 }
@@ -941,7 +941,7 @@ int bpr1cs_prove_batch_end(bpr1cs_job* job, uint8_t* proofs_out, uint8_t* commit
 int bpr1cs_prove_batch(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,
                        const uint8_t* values, const uint8_t* v_blindings, const uint8_t* rng_seeds,
                        const uint8_t* wires, size_t batch, uint8_t* proofs_out, uint8_t* commitments_out) {
-    if (!label) return BPR1CS_ERR_INVALID_ARGUMENT;
+    if (!label || (label_len & BPR1CS_LABEL_TRANSCRIPTS)) return BPR1CS_ERR_INVALID_ARGUMENT;   // (caller transcripts: bpr1cs_prove_batch_transcripts)
     const strobe s0 = label_state(label, label_len);
     return prove_batch_impl(g, c, &s0, 1, nullptr, values, v_blindings, rng_seeds, wires, batch, proofs_out, commitments_out);
 }

@@ -11,6 +11,58 @@ struct VerifyCtx {  // device state shared by the per-proof and the cross-proof 
     DevBuf<uint8_t> d_pf, d_vc, d_seed, d_label, bind;
     DevBuf<sc> chal, uk, plo, phi, wvec, gh, dpart, delta, bsc;
     DevBuf<int> fail;
+    DevBuf<strobe> d_init, d_after;   // caller transcripts (VerifyStart): the starting states and, read back, the states afterwards
+};
+// Where the proofs' transcripts start: Transcript::new(label), or - BPR1CS_LABEL_TRANSCRIPTS in label_len - the caller's own transcripts.
+// `init` is a snapshot taken once per call (a retry after OUT_OF_MEMORY replays from the same states); `after`, when set, receives
+// the state of every proof after its last inner-product challenge from the call's FIRST replay, and the extern "C" wrapper writes it
+// to the handles once the call has succeeded.
+struct VerifyStart {
+    const uint8_t* label = nullptr;
+    size_t label_len = 0;
+    const strobe* init = nullptr;
+    size_t n_init = 0;           // 0: the label form; 1: every proof from init[0]; batch: proof b from init[b]
+    strobe* after = nullptr;     // [batch] host memory, only with n_init == batch
+    VerifyStart sub(const std::vector<strobe>& gathered) const {   // a sub-batch of the same call: its own starting states, nothing written back
+        VerifyStart s = *this;
+        s.after = nullptr;
+        if (n_init > 1) { s.init = gathered.data(); s.n_init = gathered.size(); }
+        return s;
+    }
+};
+struct VerifyHandles {   // the parsed (label, label_len) of an entry point
+    VerifyStart ts;
+    std::vector<strobe> init, after;
+    bpr1cs_transcript* const* handles = nullptr;
+    int parse(const uint8_t* label, size_t label_len, size_t batch) {
+        ts.label = label; ts.label_len = label_len;
+        if (!(label_len & BPR1CS_LABEL_TRANSCRIPTS)) return BPR1CS_OK;
+        const size_t count = label_len & ~BPR1CS_LABEL_TRANSCRIPTS;
+        if (!label || batch == 0 || (count != 1 && count != batch)) return BPR1CS_ERR_INVALID_ARGUMENT;
+        handles = (bpr1cs_transcript* const*)(const void*)label;
+        for (size_t i = 0; i < count; i++)
+            if (!handles[i]) return BPR1CS_ERR_INVALID_ARGUMENT;
+        try {
+            if (count == batch && batch > 1) {   // the same handle twice: which state would it be left in?
+                std::vector<const bpr1cs_transcript*> sorted(handles, handles + count);
+                std::sort(sorted.begin(), sorted.end());
+                if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return BPR1CS_ERR_INVALID_ARGUMENT;
+            }
+            init.resize(count);
+            for (size_t i = 0; i < count; i++) init[i] = handles[i]->s;
+            if (count == batch) { after.resize(batch); ts.after = after.data(); }
+        } catch (const std::bad_alloc&) { return BPR1CS_ERR_OUT_OF_MEMORY; }
+        ts.label = (const uint8_t*)"";   // never read
+        ts.label_len = 0;
+        ts.init = init.data();
+        ts.n_init = count;
+        return BPR1CS_OK;
+    }
+    int finish(int rc) {   // the handles of a call that succeeded: where upstream's &mut transcript is when verify() returns
+        if (rc == BPR1CS_OK && ts.after)
+            for (size_t i = 0; i < after.size(); i++) handles[i]->s = after[i];
+        return rc;
+    }
 };
 static int verify_args_ok(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, const uint8_t* proofs, const uint8_t* commitments, size_t batch) {
     if (!g || !c || !label || !proofs || batch == 0 || batch > (1u << 20)) return BPR1CS_ERR_INVALID_ARGUMENT;
@@ -21,11 +73,13 @@ static int verify_args_ok(const bpr1cs_gens* g, const bpr1cs_circuit* c, const u
     return BPR1CS_OK;
 }
 // transcript replay, flattened constraints, mega-check scalars of the shared bases: gh = g_i | h_i (canonical), bsc (Montgomery)
-static void verify_front(VerifyCtx& v, const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len, const uint8_t* proofs,
+static void verify_front(VerifyCtx& v, const bpr1cs_gens* g, const bpr1cs_circuit* c, const VerifyStart& ts, const uint8_t* proofs,
                          const uint8_t* commitments, const uint8_t* verifier_rng_seeds, size_t batch, bool want_bind, dev_stream_t st) {
     const uint32_t B = v.B = (uint32_t)batch, n = v.n = c->n, m = v.m = c->m, N = v.N = c->N, lgN = v.lgN = c->lgN;
     const uint32_t p = v.p = c->p;
     v.plen = bpr1cs_proof_len(c);
+    const uint8_t* label = ts.label;
+    const size_t label_len = ts.label_len;
     v.d_pf.alloc((size_t)B * v.plen); v.d_vc.alloc((size_t)B * (m + p) * 32 + 1); v.d_seed.alloc((size_t)B * 32); v.d_label.alloc(label_len ? label_len : 1);
     dev_h2d(v.d_pf.p, proofs, (size_t)B * v.plen, st);
     if (m + p) dev_h2d(v.d_vc.p, commitments, (size_t)B * (m + p) * 32, st);   // the points and, behind them, the public inputs: one block
@@ -38,12 +92,25 @@ static void verify_front(VerifyCtx& v, const bpr1cs_gens* g, const bpr1cs_circui
     dev_zero(v.fail.p, sizeof(int) * B, st);
     K_verify_transcript kt{v.d_label.p, (uint32_t)label_len, v.d_pf.p, v.d_vc.p, v.d_seed.p, v.chal.p, v.uk.p, v.fail.p, B, m, lgN, (uint32_t)v.plen, (uint64_t)N};
     if (want_bind) { v.bind.alloc((size_t)B * 32); kt.bind = v.bind.p; }
+    const uint32_t init_stride = ts.n_init > 1 ? 1 : 0;
+    bool after_on_device = false;
+#if !defined(BPR1CS_HOSTSIM)
+    const bool host_replay = B <= VERIFY_HOST_TRANSCRIPT_MAX_PROOFS && g->opts.host_chain.load() != 0;
+#else
+    const bool host_replay = false;
+#endif
+    if (ts.init && !host_replay) {   // 216 bytes per state up and, where the handles follow their proofs, down again
+        v.d_init.alloc(ts.n_init);
+        dev_h2d(v.d_init.p, ts.init, ts.n_init * sizeof(strobe), st);
+        kt.init = v.d_init.p; kt.init_stride = init_stride;
+        if (ts.after) { v.d_after.alloc(B); kt.tr_out = v.d_after.p; after_on_device = true; }
+    }
 #if !defined(BPR1CS_HOSTSIM)
     // A handful of proofs: the transcript replay - every byte it hashes is public and in the caller's memory - runs on the calling
     // thread (the same functor, host STROBE: ~150 appends and 20 challenges of a depth-32 proof in ~50 us) and its challenges go up;
     // on the device it is one lane per proof walking the appends a state word at a time: 1.2 of a depth-32 verification's 3.3 ms.
     // (BPR1CS_OPT_HOST_CHAIN_PROOFS = 0 keeps every transcript on the device, as for the prover.)
-    if (B <= VERIFY_HOST_TRANSCRIPT_MAX_PROOFS && g->opts.host_chain.load() != 0) {
+    if (host_replay) {
         std::vector<sc> h_chal((size_t)VCH_COUNT * B), h_uk((size_t)(lgN ? lgN : 1) * 2 * B);
         std::vector<int> h_fail(B, 0);
         std::vector<uint8_t> h_bind(want_bind ? (size_t)B * 32 : 0), zero_seeds;
@@ -51,6 +118,7 @@ static void verify_front(VerifyCtx& v, const bpr1cs_gens* g, const bpr1cs_circui
         if (!seeds) { zero_seeds.assign((size_t)B * 32, 0); seeds = zero_seeds.data(); }
         K_verify_transcript kh{label, (uint32_t)label_len, proofs, commitments, seeds, h_chal.data(), h_uk.data(), h_fail.data(), B, m, lgN, (uint32_t)v.plen, (uint64_t)N};
         if (want_bind) kh.bind = h_bind.data();
+        if (ts.init) { kh.init = ts.init; kh.init_stride = init_stride; kh.tr_out = ts.after; }
         for (uint32_t b = 0; b < B; b++) kh(b);
         dev_h2d(v.chal.p, h_chal.data(), h_chal.size() * sizeof(sc), st);
         dev_h2d(v.uk.p, h_uk.data(), h_uk.size() * sizeof(sc), st);
@@ -88,20 +156,21 @@ static void verify_front(VerifyCtx& v, const bpr1cs_gens* g, const bpr1cs_circui
     if (p && !LAUNCH_WAVE_FORM(B <= FINISH_WAVE_MAX_PROOFS, B, st, k_verify_public_wave, kpub)) launch(B, kpub, st);
     launch(B, K_verify_bscalars{v.chal.p, wc, v.delta.p, v.bsc.p, B}, st);
     v.P = 8 + m + 2 * lgN;
+    if (after_on_device) dev_d2h(ts.after, v.d_after.p, (size_t)B * sizeof(strobe), st);   // (behind the front's launches: the copy waits for the stream)
 }
 
-static int verify_batch_once(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,
+static int verify_batch_once(const bpr1cs_gens* g, const bpr1cs_circuit* c, const VerifyStart& ts,
                                    const uint8_t* proofs, const uint8_t* commitments, const uint8_t* verifier_rng_seeds, size_t batch,
                                    int* ok_out) {
     if (!ok_out) return BPR1CS_ERR_INVALID_ARGUMENT;
-    int rc = verify_args_ok(g, c, label, proofs, commitments, batch);
+    int rc = verify_args_ok(g, c, ts.label, proofs, commitments, batch);
     if (rc) return rc;
     API_TRY
     dev_stream_t st = g->stream;
     CallScope scope(st);
     MsmStats stats;
     VerifyCtx v;
-    verify_front(v, g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, false, st);
+    verify_front(v, g, c, ts, proofs, commitments, verifier_rng_seeds, batch, false, st);
     const uint32_t B = v.B, N = v.N, baseG = 2, baseH = 2 + g->cap;
     DevBuf<ge> partial;
     MsmPlan plan;
@@ -194,19 +263,19 @@ static void verify_combine(CombinedCtx& k, VerifyCtx& v, const uint8_t* batch_se
 // Cross-proof batched verification: one identity test for the whole batch (and, summed over ranks, for the whole job).
 // Returns this rank's partial point; the caller adds the ranks' points (bpr1cs_points_sum) and accepts iff the sum
 // is the identity (32 zero bytes) and every rank reported `wellformed`.
-static int verify_batch_combined_once(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,
+static int verify_batch_combined_once(const bpr1cs_gens* g, const bpr1cs_circuit* c, const VerifyStart& ts,
                                             const uint8_t* proofs, const uint8_t* commitments, const uint8_t* verifier_rng_seeds,
                                             const uint8_t* batch_seed, uint64_t index_base, size_t batch, uint8_t* partial_point_out,
                                             int* wellformed_out) {
     if (!batch_seed || !partial_point_out || !wellformed_out) return BPR1CS_ERR_INVALID_ARGUMENT;
-    int rc = verify_args_ok(g, c, label, proofs, commitments, batch);
+    int rc = verify_args_ok(g, c, ts.label, proofs, commitments, batch);
     if (rc) return rc;
     API_TRY
     dev_stream_t st = g->stream;
     CallScope scope(st);
     MsmStats stats;
     VerifyCtx v;
-    verify_front(v, g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, true, st);
+    verify_front(v, g, c, ts, proofs, commitments, verifier_rng_seeds, batch, true, st);
     CombinedCtx k;
     verify_combine(k, v, batch_seed, index_base, st);
     const uint32_t N = v.N, baseG = 2, baseH = 2 + g->cap;
@@ -267,7 +336,7 @@ extern "C" int bpr1cs_sim_group_combine_grid(uint64_t rows, uint64_t NG, uint32_
 // proofs, a failing range of one proof rejects it.  Nothing is uploaded again and the per-proof path is not taken.
 // -> ok_out[B], pfail[B] (proof is malformed)
 struct BisectRange { uint32_t lo, hi, pt; };   // a failing range of more than one proof; pt: where its S sits among the depth's points
-static int verify_batch_bisect_once(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,
+static int verify_batch_bisect_once(const bpr1cs_gens* g, const bpr1cs_circuit* c, const VerifyStart& ts,
                                     const uint8_t* proofs, const uint8_t* commitments, const uint8_t* verifier_rng_seeds, size_t batch,
                                     uint32_t G, bool descend, int* ok_out, std::vector<int>& pfail) {
     API_TRY
@@ -275,7 +344,7 @@ static int verify_batch_bisect_once(const bpr1cs_gens* g, const bpr1cs_circuit* 
     CallScope scope(st);
     MsmStats stats;
     VerifyCtx v;
-    verify_front(v, g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, true, st);
+    verify_front(v, g, c, ts, proofs, commitments, verifier_rng_seeds, batch, true, st);
     const uint32_t B = v.B, N = v.N, NG = (B + G - 1) / G, baseG = 2, baseH = 2 + g->cap;
     // the entry point has no batch seed of its own: the first proof's verifier seed (zeros with none), bound to the whole batch by the digest
     uint8_t bseed[32] = {0};
@@ -353,14 +422,14 @@ static int verify_batch_bisect_once(const bpr1cs_gens* g, const bpr1cs_circuit* 
     return BPR1CS_OK;
     API_CATCH
 }
-static int verify_batch_grouped_once(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,
+static int verify_batch_grouped_once(const bpr1cs_gens* g, const bpr1cs_circuit* c, const VerifyStart& ts,
                                      const uint8_t* proofs, const uint8_t* commitments, const uint8_t* verifier_rng_seeds, size_t batch,
                                      uint32_t G, int mode, int* ok_out) {
     if (!ok_out) return BPR1CS_ERR_INVALID_ARGUMENT;
-    int rc = verify_args_ok(g, c, label, proofs, commitments, batch);
+    int rc = verify_args_ok(g, c, ts.label, proofs, commitments, batch);
     if (rc) return rc;
     std::vector<int> pfail;
-    rc = verify_batch_bisect_once(g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, G,
+    rc = verify_batch_bisect_once(g, c, ts, proofs, commitments, verifier_rng_seeds, batch, G,
                                   mode == BPR1CS_VERIFY_GROUP_FALLBACK_BISECT, ok_out, pfail);
     if (rc || mode != BPR1CS_VERIFY_GROUP_FALLBACK_RECHECK) return rc;
     API_TRY
@@ -379,7 +448,9 @@ static int verify_batch_grouped_once(const bpr1cs_gens* g, const bpr1cs_circuit*
         if (ulen) memcpy(sc_.data() + redo.size() * clen + i * ulen, pub + redo[i] * ulen, ulen);
         if (verifier_rng_seeds) memcpy(ss.data() + i * 32, verifier_rng_seeds + redo[i] * 32, 32);
     }
-    rc = verify_batch_once(g, c, label, label_len, sp.data(), sc_.data(), verifier_rng_seeds ? ss.data() : nullptr, redo.size(), sok.data());
+    std::vector<strobe> st0(ts.n_init > 1 ? redo.size() : 0);   // per-proof starting states travel with their proofs
+    for (size_t i = 0; i < st0.size(); i++) st0[i] = ts.init[redo[i]];
+    rc = verify_batch_once(g, c, ts.sub(st0), sp.data(), sc_.data(), verifier_rng_seeds ? ss.data() : nullptr, redo.size(), sok.data());
     if (rc) return rc;
     for (size_t i = 0; i < redo.size(); i++) ok_out[redo[i]] = sok[i];
     return BPR1CS_OK;
@@ -389,18 +460,18 @@ static int verify_batch_grouped_once(const bpr1cs_gens* g, const bpr1cs_circuit*
 // Multi-GPU form of the batched verifier: instead of evaluating the shared-base MSM itself, a rank
 // returns its combined scalar vector; the ranks add their vectors (all_gather / all_reduce of 2N+2 scalars, ~2 MB at
 // N = 32768), each evaluates 1/world of the bases with bpr1cs_msm_fixed, and the points are gathered and summed.
-static int verify_batch_scalars_once(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,
+static int verify_batch_scalars_once(const bpr1cs_gens* g, const bpr1cs_circuit* c, const VerifyStart& ts,
                                            const uint8_t* proofs, const uint8_t* commitments, const uint8_t* verifier_rng_seeds,
                                            const uint8_t* batch_seed, uint64_t index_base, size_t batch, uint8_t* combined_scalars_out,
                                            uint8_t* own_points_sum_out, int* wellformed_out) {
     if (!batch_seed || !combined_scalars_out || !own_points_sum_out || !wellformed_out) return BPR1CS_ERR_INVALID_ARGUMENT;
-    int rc = verify_args_ok(g, c, label, proofs, commitments, batch);
+    int rc = verify_args_ok(g, c, ts.label, proofs, commitments, batch);
     if (rc) return rc;
     API_TRY
     dev_stream_t st = g->stream;
     CallScope scope(st);
     VerifyCtx v;
-    verify_front(v, g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, true, st);
+    verify_front(v, g, c, ts, proofs, commitments, verifier_rng_seeds, batch, true, st);
     CombinedCtx k;
     verify_combine(k, v, batch_seed, index_base, st);
     const uint32_t N = v.N;
@@ -447,25 +518,42 @@ static int with_scratch_retry(const bpr1cs_gens* g, F&& once) {
     }
     return rc;
 }
+// The entry points parse (label, label_len) ONCE (VerifyHandles), run - and possibly re-run - on the snapshot, and write the handles
+// of a transcripts call back only when the call has succeeded.
 extern "C" int bpr1cs_verify_batch(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,
                                    const uint8_t* proofs, const uint8_t* commitments, const uint8_t* verifier_rng_seeds, size_t batch,
                                    int* ok_out) {
+    VerifyHandles h;
+    if (int rc = h.parse(label, label_len, batch)) return rc;
+    const VerifyStart& ts = h.ts;
     const int G = g ? g->opts.verify_group.load() : 0;
     if (G >= 2 && batch >= 2) {
         const int mode = g->opts.verify_group_fallback.load();
-        return with_scratch_retry(g, [&] { return verify_batch_grouped_once(g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, (uint32_t)G, mode, ok_out); });
+        return h.finish(with_scratch_retry(g, [&] { return verify_batch_grouped_once(g, c, ts, proofs, commitments, verifier_rng_seeds, batch, (uint32_t)G, mode, ok_out); }));
     }
-    return with_scratch_retry(g, [&] { return verify_batch_once(g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch, ok_out); });
+    return h.finish(with_scratch_retry(g, [&] { return verify_batch_once(g, c, ts, proofs, commitments, verifier_rng_seeds, batch, ok_out); }));
 }
 extern "C" int bpr1cs_verify_batch_combined(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,
                                             const uint8_t* proofs, const uint8_t* commitments, const uint8_t* verifier_rng_seeds,
                                             const uint8_t* batch_seed, uint64_t index_base, size_t batch, uint8_t* partial_point_out,
                                             int* wellformed_out) {
-    return with_scratch_retry(g, [&] { return verify_batch_combined_once(g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch_seed, index_base, batch, partial_point_out, wellformed_out); });
+    VerifyHandles h;
+    if (int rc = h.parse(label, label_len, batch)) return rc;
+    const VerifyStart& ts = h.ts;
+    return h.finish(with_scratch_retry(g, [&] { return verify_batch_combined_once(g, c, ts, proofs, commitments, verifier_rng_seeds, batch_seed, index_base, batch, partial_point_out, wellformed_out); }));
+}
+// (the sharded form parses for itself: its handles are written when the whole exchange has succeeded, not when this step has)
+static int verify_batch_scalars_parsed(const bpr1cs_gens* g, const bpr1cs_circuit* c, const VerifyStart& ts,
+                                       const uint8_t* proofs, const uint8_t* commitments, const uint8_t* verifier_rng_seeds,
+                                       const uint8_t* batch_seed, uint64_t index_base, size_t batch, uint8_t* combined_scalars_out,
+                                       uint8_t* own_points_sum_out, int* wellformed_out) {
+    return with_scratch_retry(g, [&] { return verify_batch_scalars_once(g, c, ts, proofs, commitments, verifier_rng_seeds, batch_seed, index_base, batch, combined_scalars_out, own_points_sum_out, wellformed_out); });
 }
 extern "C" int bpr1cs_verify_batch_scalars(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,
                                            const uint8_t* proofs, const uint8_t* commitments, const uint8_t* verifier_rng_seeds,
                                            const uint8_t* batch_seed, uint64_t index_base, size_t batch, uint8_t* combined_scalars_out,
                                            uint8_t* own_points_sum_out, int* wellformed_out) {
-    return with_scratch_retry(g, [&] { return verify_batch_scalars_once(g, c, label, label_len, proofs, commitments, verifier_rng_seeds, batch_seed, index_base, batch, combined_scalars_out, own_points_sum_out, wellformed_out); });
+    VerifyHandles h;
+    if (int rc = h.parse(label, label_len, batch)) return rc;
+    return h.finish(verify_batch_scalars_parsed(g, c, h.ts, proofs, commitments, verifier_rng_seeds, batch_seed, index_base, batch, combined_scalars_out, own_points_sum_out, wellformed_out));
 }

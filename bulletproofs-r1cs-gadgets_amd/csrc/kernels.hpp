@@ -1805,6 +1805,11 @@ struct K_verify_transcript {  // gid = b
     uint32_t B, m, lgN, plen;
     uint64_t padded_n;
     uint8_t* bind = nullptr;  // optional [B][32]
+    // the caller's transcripts (BPR1CS_LABEL_TRANSCRIPTS), as K_transcript_init's: proof b starts from init[b * init_stride] in place of
+    // Transcript::new(label).  All null / zero in the label form.
+    const strobe* init = nullptr;
+    uint32_t init_stride = 0;
+    strobe* tr_out = nullptr;  // optional [B]: the transcript after the last inner-product challenge (where upstream's &mut transcript is after verify())
     HD void operator()(uint32_t b) const {
         const uint8_t* pf = proofs + (size_t)b * plen;
         int bad = pf[0] != 0;  // one-phase format byte (R1CSProof::from_bytes -> FormatError)
@@ -1812,7 +1817,8 @@ struct K_verify_transcript {  // gid = b
         bad |= !scalar_bytes_canonical(el + 8 * 32) | !scalar_bytes_canonical(el + 9 * 32) | !scalar_bytes_canonical(el + 10 * 32);
         bad |= !scalar_bytes_canonical(el + (11 + 2 * lgN) * 32) | !scalar_bytes_canonical(el + (12 + 2 * lgN) * 32);
         strobe s;
-        merlin_new(s, label, label_len);
+        if (init) s = init[(size_t)b * init_stride];
+        else merlin_new(s, label, label_len);
         merlin_append(s, "dom-sep", 7, (const uint8_t*)"r1cs v1", 7);
         for (uint32_t j = 0; j < m; j++) merlin_append(s, "V", 1, Vc + ((size_t)b * m + j) * 32, 32);
         merlin_append_u64(s, "m", 1, m);
@@ -1851,6 +1857,7 @@ struct K_verify_transcript {  // gid = b
             sc uu = merlin_challenge_scalar(s, "u", 1);
             uk[((size_t)k * 2 + 0) * B + b] = uu;
         }
+        if (tr_out) tr_out[b] = s;  // (the same state from every lane of a lockstep launch; the RNG below works on s itself, so: here)
         // the inverses of y and of every u_k from ONE inversion (Montgomery's trick, as upstream's verifier: Scalar::batch_invert):
         // slot [k][1] holds the product of what came before u_k on the way up and u_k^-1 on the way down.  (One safegcd per round was
         // 0.65 of the 1.7 ms this kernel takes for one depth-32 proof.)  A zero challenge - probability 2^-252 - zeroes them all.

@@ -103,7 +103,6 @@ R1CSProof Prover::prove(const BulletproofGens& bp_gens) {
         rc = bpr1cs_prove_batch_transcripts(bp_gens.h, c, ts, 1, vals.data(), bls.data(), seed.data(), wires.data(), 1, bytes.data(), comm_bytes.data());
         if (rc == 0 && ledger && !defer_commitments) ledger->fill(comm_bytes.data(), m);   // commitments nobody has read yet: the job computed them
     }
-    transcript.fresh = false;
     bpr1cs_circuit_destroy(c);
     if (dbg) fprintf(stderr, "front: circuit %.2f ms, witness export %.2f, chain take %.2f, device call + wipe %.2f\n", 1e3 * (t1 - t0), 1e3 * (t_exp - t1), 1e3 * (t_take - t_exp), 1e3 * (now_s() - t_take));
     if (seconds) { seconds[0] += t1 - t0; seconds[1] += now_s() - t1; }
@@ -112,10 +111,10 @@ R1CSProof Prover::prove(const BulletproofGens& bp_gens) {
 }
 
 void Verifier::verify(const R1CSProof& proof, const PedersenGens&, const BulletproofGens& bp_gens, const std::array<uint8_t, 32>* rng_seed) {
-    // bpr1cs_verify_batch starts from Transcript::new(label) - all the reference ever hands over (its call sites create the
-    // transcript on the line before, e.g. src/gadget_vsmt_4.rs:442-443); a transcript that already holds messages is refused
-    // rather than silently mis-verified (as tools/rust_shim/verifier.rs)
-    if (!transcript.fresh) throw R1CSError::GadgetError("Verifier::new on a transcript that already holds messages is not supported by the device verifier");
+    // The proof is replayed from the caller's transcript, whatever it holds (BPR1CS_LABEL_TRANSCRIPTS: a fresh Transcript::new(label) - all
+    // the reference's call sites hand over, e.g. src/gadget_vsmt_4.rs:442-443 - is one such state), and the handle is left where
+    // upstream's `&mut` transcript is when verify() returns: a second verify on the same Transcript is the protocol's next proof
+    // (as tools/rust_shim/verifier.rs).  One proof replays on the calling thread either way.
     size_t n = num_vars, padded = 1;
     while (padded < n) padded <<= 1;
     if (bp_gens.gens_capacity < padded) throw R1CSError::InvalidGeneratorsLength();
@@ -142,10 +141,9 @@ void Verifier::verify(const R1CSProof& proof, const PedersenGens&, const Bulletp
         for (auto& x : seed) x = (uint8_t)rd();
     }
     int ok = 0;
-    rc = bpr1cs_verify_batch(bp_gens.h, c, (const uint8_t*)transcript.label.data(), transcript.label.size(), bytes.data(),
-                             comms.data(), seed.data(), 1, &ok);
+    bpr1cs_transcript* ts[1] = {transcript.h};
+    rc = bpr1cs_verify_batch(bp_gens.h, c, (const uint8_t*)ts, BPR1CS_LABEL_TRANSCRIPTS | 1, bytes.data(), comms.data(), seed.data(), 1, &ok);
     bpr1cs_circuit_destroy(c);
-    transcript.fresh = false;
     if (rc) throw R1CSError::Backend(rc);
     if (!ok) throw R1CSError::VerificationError();
 }

@@ -352,19 +352,18 @@ public:
 
 // merlin::Transcript as the reference uses it: `Transcript::new(b"VSMT")` (src/gadget_vsmt_4.rs:390), handed to Prover / Verifier as
 // `&mut`.  The state is the library's Merlin object (bpr1cs_transcript: STROBE-128 over Keccak-f[1600], the SAME state the prover
-// kernels start from), so a transcript that already holds messages keeps its meaning for Prover::new (bpr1cs_prove_batch_transcripts)
-// and is advanced to the state upstream's `&mut` transcript has when prove() returns - exactly what tools/rust_shim/transcript.rs does.
+// kernels start from), so a transcript that is not fresh keeps its meaning for Prover::new (bpr1cs_prove_batch_transcripts) and for
+// Verifier::new (bpr1cs_verify_batch with BPR1CS_LABEL_TRANSCRIPTS), and is advanced to the state upstream's `&mut` transcript has when
+// prove() / verify() returns - exactly what tools/rust_shim/transcript.rs does.
 struct Transcript {
     std::string label;
     bpr1cs_transcript* h = nullptr;
-    bool fresh = true;   // nothing appended since new(): the device verifier takes a label (all the reference's 30 call sites need)
     explicit Transcript(const std::string& l) : label(l) { h = bpr1cs_transcript_new((const uint8_t*)label.data(), label.size()); }
     Transcript(const char* l, size_t n) : label(l, n) { h = bpr1cs_transcript_new((const uint8_t*)label.data(), label.size()); }
     Transcript(const Transcript&) = delete;
     Transcript& operator=(const Transcript&) = delete;
     ~Transcript() { bpr1cs_transcript_free(h); }
     void append_message(const std::string& lbl, const uint8_t* msg, size_t len) {
-        fresh = false;
         bpr1cs_transcript_append_message(h, (const uint8_t*)lbl.data(), lbl.size(), msg, len);
     }
     void append_u64(const std::string& lbl, uint64_t x) {
@@ -373,7 +372,6 @@ struct Transcript {
         append_message(lbl, b, 8);
     }
     void challenge_bytes(const std::string& lbl, uint8_t* dest, size_t len) {
-        fresh = false;
         bpr1cs_transcript_challenge_bytes(h, (const uint8_t*)lbl.data(), lbl.size(), dest, len);
     }
 };

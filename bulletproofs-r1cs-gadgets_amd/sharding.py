@@ -68,7 +68,7 @@ def make_comm(bp, rank, world, group=None, device=None, lib=None):
     return bp.Comm(uid, rank, world, lib=lib)
 
 
-def verify_sharded(bp, gens, circuit, label, proofs, commitments, batch, rank, world, index_base, batch_seed=None, group=None, device=None, comm=None):
+def verify_sharded(bp, gens, circuit, label, proofs, commitments, batch, rank, world, index_base, batch_seed=None, group=None, device=None, comm=None, transcripts=None):
     """Batched verification of a job sharded over `world` ranks with the shared-base MSM computed ONCE per job.
     With `comm` (bp.Comm, an RCCL communicator) this is ONE call into the library: bpr1cs_verify_batch_sharded does the
     steps below with ncclAllGather over xGMI.  Without it the same steps run here with torch.distributed collectives - the
@@ -79,10 +79,11 @@ def verify_sharded(bp, gens, circuit, label, proofs, commitments, batch, rank, w
       3. every rank evaluates its 1/world slice of the bases with bpr1cs_msm_fixed;
       4. all_gather of (slice point, own-points sum, well-formed flag): 65 bytes per rank; accept iff the sum of all
          points is the identity and every rank was well-formed.
-    Every rank returns the same verdict."""
+    Every rank returns the same verdict.  `transcripts` (with label = None): this rank's proofs start from the caller's transcripts
+    (bp.verify_batch_scalars)."""
     if comm is not None:
         try:
-            return bp.verify_batch_sharded(gens, circuit, label, proofs, commitments, batch, comm, batch_seed, index_base)
+            return bp.verify_batch_sharded(gens, circuit, label, proofs, commitments, batch, comm, batch_seed, index_base, transcripts=transcripts)
         except Exception:
             return False
     # a rank that fails locally still takes part in both collectives (with a zero vector and a "not well-formed" flag):
@@ -90,7 +91,7 @@ def verify_sharded(bp, gens, circuit, label, proofs, commitments, batch, rank, w
     N = 1 << max(0, (circuit.n - 1).bit_length())
     nb = 2 * N + 2
     try:
-        vec, own, wf = bp.verify_batch_scalars(gens, circuit, label, proofs, commitments, batch, batch_seed=batch_seed, index_base=index_base)
+        vec, own, wf = bp.verify_batch_scalars(gens, circuit, label, proofs, commitments, batch, batch_seed=batch_seed, index_base=index_base, transcripts=transcripts)
     except Exception:
         vec, own, wf = bytes(32 * nb), bytes(32), False
     gathered = _all_gather_bytes(vec, group, device)

@@ -438,7 +438,27 @@ int bpr1cs_prove_batch_end(bpr1cs_job* job, uint8_t* proofs_out, uint8_t* commit
  *   verifier_rng_seeds   batch * 32 or NULL (zeros): the 32 bytes upstream draws from thread_rng() for `r`
  * On a handle with BPR1CS_OPT_VERIFY_GROUP = G >= 2 a batch of 2 or more proofs is checked group by group - one combined identity
  * test per G consecutive proofs, the per-proof check only inside a group that fails: per-proof verdicts at close to the cost of
- * bpr1cs_verify_batch_combined while the proofs are good (see the option for the weights and BPR1CS_OPT_VERIFY_GROUP_FALLBACK). */
+ * bpr1cs_verify_batch_combined while the proofs are good (see the option for the weights and BPR1CS_OPT_VERIFY_GROUP_FALLBACK).
+ *
+ * THE CALLER'S TRANSCRIPTS (Verifier::new(&mut transcript) on a transcript that is not fresh: it holds a session id, a nonce, the
+ * proof before this one): bpr1cs_verify_batch, _combined, _scalars and _sharded take them in the two arguments they have.  With
+ * BPR1CS_LABEL_TRANSCRIPTS set in `label_len`, `label` is a bpr1cs_transcript* const* (cast to const uint8_t*) of
+ * count = label_len & ~BPR1CS_LABEL_TRANSCRIPTS handles, count = batch or 1:
+ *   - proof b is replayed from the state of handle b (count = 1: every proof from handle 0) in place of Transcript::new(label);
+ *     everything from ("dom-sep", "r1cs v1") on is what it is in the label form;
+ *   - when the call returns BPR1CS_OK and count = batch (a batch of one with its one handle included), handle b is left in the state
+ *     after proof b's last inner-product challenge: where upstream's `&mut` transcript is when verify() returns (its build_rng works
+ *     on a clone) and where bpr1cs_prove_batch_transcripts leaves the prover's handle - so the next proof of a protocol is proved
+ *     and verified on the same pair of transcripts.  The handle of a REJECTED or malformed proof is advanced in the same way (the replay
+ *     absorbs every element whatever it finds; upstream leaves the transcript wherever the error struck): only the handle of an
+ *     accepted proof is meaningful to continue from;
+ *   - count = 1 < batch leaves the handle untouched, and a call that returns an error touches no handle;
+ *   - BPR1CS_ERR_INVALID_ARGUMENT: a count other than 1 or batch, a NULL handle, the same handle twice when count = batch (which
+ *     state would it be left in?), and the flag on bpr1cs_prove_batch / bpr1cs_prove_batch_begin (bpr1cs_prove_batch_transcripts is
+ *     their form of it).
+ * The grouped form seeds its weights as in the label form.  A transcript's contents are public for a verifier: nothing is wiped.
+ * Without the flag every call is what it was (a label_len of 2^63 or more has never been a label). */
+#define BPR1CS_LABEL_TRANSCRIPTS ((size_t)1 << (sizeof(size_t) * 8 - 1))
 int bpr1cs_verify_batch(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uint8_t* label, size_t label_len,
                         const uint8_t* proofs, const uint8_t* commitments, const uint8_t* verifier_rng_seeds, size_t batch,
                         int* ok_out);
@@ -448,7 +468,8 @@ int bpr1cs_verify_batch(const bpr1cs_gens* g, const bpr1cs_circuit* c, const uin
  * shared bases B, B~, G_i, H_i get ONE combined scalar each (sum_j rho_j * scalar_j) and a single fixed-base MSM; only
  * the proofs' own points are handled per proof.  The weights, in Merlin transcripts (<- appends, u64 = 8 bytes LE):
  *   bind_j  = the proof's own verifier transcript after its last inner-product challenge, cloned,
- *             <- ("ipp_a", a) <- ("ipp_b", b); challenge_bytes("bpr1cs-bind", 32)   (every byte of proof and commitments)
+ *             <- ("ipp_a", a) <- ("ipp_b", b); challenge_bytes("bpr1cs-bind", 32)   (every byte of proof and commitments - and, the
+ *             clone being of the proof's OWN transcript, the state it started from: a label or the caller's transcript alike)
  *   leaf_g  = Transcript("bpr1cs batch leaf") <- u64("leaf", g) <- ("proof", bind_j) for the 32 proofs j = 32g .. 32g+31
  *             (the last leaf may be short); challenge_bytes("leaf", 32).  A circuit with p > 0 public inputs: after each
  *             proof's ("proof", bind_j) the leaf absorbs ("public", p_j,0 || ... || p_j,p-1) (p x 32 bytes) - the proof's own

@@ -10,6 +10,7 @@ pub const BPR1CS_ERR_NO_DEVICE: i32 = -16;
 pub const BPR1CS_ERR_INVALID_ARGUMENT: i32 = -17;
 pub const BPR1CS_ERR_DEVICE: i32 = -18;
 pub const BPR1CS_ERR_OUT_OF_MEMORY: i32 = -19;
+pub const BPR1CS_LABEL_TRANSCRIPTS: usize = 1 << (usize::BITS - 1);
 #[repr(C)] pub struct bpr1cs_gens { _private: [u8; 0] }
 #[repr(C)] pub struct bpr1cs_circuit { _private: [u8; 0] }
 #[repr(C)] pub struct bpr1cs_transcript { _private: [u8; 0] }

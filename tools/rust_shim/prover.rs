@@ -116,7 +116,6 @@ impl<'t, 'g> Prover<'t, 'g> {
         };
         unsafe { ffi::bpr1cs_circuit_destroy(circuit) };
         // (with ONE transcript handle for a batch of one the library advances that handle: n_transcripts == batch)
-        self.transcript.fresh = false;
         check(rc)?;
         R1CSProof::from_bytes(&proof)
     }

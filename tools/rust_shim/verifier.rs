@@ -39,11 +39,9 @@ impl<'t> Verifier<'t> {
     }
     /// reference: `verifier.verify(&proof, &pc_gens, &bp_gens).is_ok()` src/gadget_vsmt_4.rs:479
     pub fn verify(self, proof: &R1CSProof, _pc_gens: &PedersenGens, bp_gens: &BulletproofGens) -> Result<(), R1CSError> {
-        // bpr1cs_verify_batch starts from Transcript::new(label): all the reference ever hands over (its 30 call sites create the
-        // transcript on the line before); a transcript with earlier messages is refused rather than silently mis-verified
-        if !self.transcript.fresh {
-            return Err(R1CSError::GadgetError { description: "Verifier::new on a transcript that already holds messages is not supported by the device verifier".into() });
-        }
+        // The proof is replayed from the caller's transcript, whatever it holds (BPR1CS_LABEL_TRANSCRIPTS: the handle rides in the label
+        // argument), and the handle is left where upstream's `&mut` transcript is when verify() returns - a fresh Transcript::new(label),
+        // all the reference's 30 call sites hand over, is one such state.  Only after Ok(()) is the transcript meaningful to continue from.
         let mut row_off = vec![0u32];
         let mut term_var = Vec::<u32>::new();
         let mut term_coeff = Vec::<u8>::new();
@@ -70,12 +68,12 @@ impl<'t> Verifier<'t> {
         let expected = unsafe { ffi::bpr1cs_proof_len(circuit) };
         let rc = if bytes.len() != expected { ffi::BPR1CS_ERR_FORMAT } else {
             unsafe {
-                ffi::bpr1cs_verify_batch(bp_gens.handle.0, circuit, self.transcript.label.as_ptr(), self.transcript.label.len(), bytes.as_ptr(),
+                let handles = [self.transcript.h];
+                ffi::bpr1cs_verify_batch(bp_gens.handle.0, circuit, handles.as_ptr() as *const u8, ffi::BPR1CS_LABEL_TRANSCRIPTS | 1, bytes.as_ptr(),
                                         commitments.as_ptr(), seed.as_ptr(), 1, &mut ok)
             }
         };
         unsafe { ffi::bpr1cs_circuit_destroy(circuit) };
-        self.transcript.fresh = false;
         check(rc)?;
         if ok == 1 { Ok(()) } else { Err(R1CSError::VerificationError) }
     }
